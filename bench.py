@@ -2,8 +2,8 @@
 """Headline benchmark: BERT-large pretraining tokens/s + ResNet-50 training images/s, whole job.
 
 Metric / config from BASELINE.json ("samples/sec ResNet-50 + tokens/sec BERT-large, whole
-node, 1/2/4/8 MI355X").  One invocation measures BOTH halves, one after the other in the
-same rank processes:
+node, 1/2/4/8 MI355X").  One ``--full`` invocation measures BOTH halves, one after the other
+in the same rank processes (a plain one: the first, the headline):
 
 * BERT-large (24 x 1024, 16 heads, vocab 30522), seq 128, 76 masked-LM slots per sequence
   (max_predictions_per_seq, reference run_ddp_bert_pretrain_phase1.sh:72), per-GPU batch 256,
@@ -21,8 +21,20 @@ barrier + torch.cuda.synchronize() on both sides; the max time over ranks is rep
 timed step is forward + backward + bucketed gradient all-reduce + optimizer step (+ LR
 schedule for BERT).
 
+A plain run measures the headline only: the BERT-large half (set-up, W warm-up steps, K timed
+steps, one JSON line).  ``--full`` adds everything else: the ResNet-50 half, the stock-PyTorch
+baseline of each half (``vs_baseline``), the ResNet kernel audit and the per-bucket collective
+timeline at world size > 1 (one extra untimed step each).
+
+``--dump-outputs DIR`` writes what the timed path computed in its last timed step as
+``DIR/<model>_loss.npy`` (the step's loss) and ``DIR/<model>_weights.npy`` (the updated weights:
+all of them, or a fixed seeded sample of 4M elements of the flat weight buffer), float32.  The
+weights, the batch and the dropout stream are seeded, so two builds can be compared output
+for output.
+
 Launch:
     python bench.py --gpus N --steps K --warmup W          # spawns N rank processes itself
+    python bench.py --gpus N --steps K --warmup W --full   # both halves + baselines + audits
     torchrun --nproc-per-node N bench.py --gpus N ...       # or ranks from the environment
 Options: ``--model bert-large|resnet50`` (one half only), ``--impl eager`` (stock PyTorch
 baseline: HF BertForPreTraining + SDPA + DDP + per-tensor LAMB / nn.Conv2d+BatchNorm2d
@@ -60,10 +72,17 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--model", default="all", choices=["all", "bert-large", "bert-base", "resnet50", "tiny"])
     ap.add_argument("--impl", default="native", choices=["native", "eager"])
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: with --model all / tiny the ResNet half too, "
+                         "the stock-PyTorch baseline (--baseline-steps / --compare-eager), the ResNet kernel "
+                         "audit and the gradient-bucket timeline (one extra untimed step each)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's loss and the updated weights "
+                         "(all, or a fixed seeded sample) as DIR/<model>_loss.npy / DIR/<model>_weights.npy")
     ap.add_argument("--compare-eager", action="store_true",
-                    help="also run the stock-PyTorch baseline of the same config for the full K / W steps")
+                    help="--full: also run the stock-PyTorch baseline of the same config for the full K / W steps")
     ap.add_argument("--baseline-steps", type=int, default=-1,
-                    help="native runs: after the native halves, time this many steps of the same-config stock "
+                    help="--full, native runs: after the native halves, time this many steps of the same-config stock "
                          "PyTorch-ROCm eager step (SURVEY.md section 6 item 3; BASELINE.json publishes no "
                          "number) and report native / eager as vs_baseline; 0 = skip; -1 (default) = 5 at "
                          "world size 1, skipped above (a stock-DDP failure on one rank would leave the others "
@@ -105,7 +124,10 @@ def parse(argv=None):
     ap.add_argument("--tunableop", default=os.environ.get("CLOUDTIK_BENCH_TUNABLEOP", "use"),
                     choices=["off", "use", "tune"],
                     help="hipBLASLt solution selection via PyTorch TunableOp (results shipped in-tree)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and (args.compare_eager or args.baseline_steps > 0):
+        ap.error("--compare-eager / --baseline-steps time a second implementation: add --full")
+    return args
 
 
 # ------------------------------------------------------------------ rank launcher
@@ -329,7 +351,8 @@ def build_bert(args, rank, world, device, kind):
                 unit="tokens/s", items_per_step=B * S,
                 metric="bert_large_pretrain_tokens_per_sec" if kind in ("bert-large", "tiny")
                 else "bert_base_pretrain_tokens_per_sec",
-                optimizer="fused LAMB (HIP)", impl="native", plan=bucket_plan(ddp), bucketer=ddp)
+                optimizer="fused LAMB (HIP)", impl="native", plan=bucket_plan(ddp), bucketer=ddp,
+                weights=lambda: space.model[:space.used])
     return step, close, info
 
 
@@ -374,7 +397,8 @@ def build_resnet(args, rank, world, device, kind):
     info = dict(model="resnet50" if not tiny else "resnet-tiny", per_gpu_batch=B, seq_len=None,
                 unit="images/s", items_per_step=B, metric="resnet50_train_images_per_sec",
                 optimizer="fused SGD (HIP)", impl="native", image_size=R, plan=bucket_plan(ddp),
-                hip_graph=bool(graph), bucketer=None if graph else ddp)
+                hip_graph=bool(graph), bucketer=None if graph else ddp,
+                weights=lambda: space.model[:space.used])
     return step, ddp.remove, info
 
 
@@ -422,7 +446,8 @@ def build_bert_eager(args, rank, world, device, kind):
 
     info = dict(model=kind if not tiny else "bert-tiny", per_gpu_batch=B, seq_len=S, max_pred=P, unit="tokens/s",
                 items_per_step=B * S, metric="bert_large_pretrain_tokens_per_sec",
-                optimizer="per-tensor LAMB (stock PyTorch)", impl="eager")
+                optimizer="per-tensor LAMB (stock PyTorch)", impl="eager",
+                weights=lambda: torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
     return step, (lambda: None), info
 
 
@@ -458,7 +483,8 @@ def build_resnet_eager(args, rank, world, device, kind):
 
     info = dict(model="resnet50" if not tiny else "resnet-tiny", per_gpu_batch=B, seq_len=None, unit="images/s",
                 items_per_step=B, metric="resnet50_train_images_per_sec", optimizer="torch.optim.SGD (foreach)",
-                impl="eager", image_size=R)
+                impl="eager", image_size=R,
+                weights=lambda: torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
     return step, (lambda: None), info
 
 
@@ -572,9 +598,33 @@ def bucket_timeline(step, bucketer, device):
         bucketer.trace = False
 
 
-def timed(step, args, rank, world, device, audit=False, bucketer=None):
+DUMP_SAMPLE = 4 << 20          # --dump-outputs keeps at most this many weights (16 MB as float32)
+
+
+def collect_outputs(loss, weights):
+    """--dump-outputs: what the last timed step handed back, as float32 numpy arrays: its loss
+    and the weights it updated (a flat tensor; above DUMP_SAMPLE elements a fixed seeded sample
+    in ascending index order, the same indices in every run of the same configuration)."""
+    import torch
+    w = weights().detach()
+    if w.numel() > DUMP_SAMPLE:
+        idx = torch.randint(0, w.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(2024))
+        w = w[idx.sort().values.to(w.device)]
+    return {"loss": loss.detach().float().reshape(1).cpu().numpy(), "weights": w.float().cpu().numpy()}
+
+
+def write_outputs(directory, model, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{model.replace('-', '_')}_{name}.npy"), a)
+
+
+def timed(step, args, rank, world, device, audit=False, bucketer=None, weights=None):
     """W warm-up steps, then K timed steps between barrier+sync brackets.  Returns
     (max elapsed over ranks, per-rank elapsed list, last loss, per-step ms, audit).
+    ``weights`` (--dump-outputs): the outputs of the last timed step are collected right after
+    the timed region, before any untimed extra step, as ``audit["dump"]``.
 
     Per-step times come from HIP events recorded between the steps on the compute stream
     (no host synchronisation inside the timed loop); the headline is the host clock around
@@ -620,6 +670,7 @@ def timed(step, args, rank, world, device, audit=False, bucketer=None):
     sync()
     el = time.perf_counter() - t0
     telemetry = tele.stop()
+    dump = collect_outputs(loss, weights) if weights is not None else None
     if cuda:
         step_ms = [events[i].elapsed_time(events[i + 1]) for i in range(args.steps)]
     else:
@@ -632,6 +683,8 @@ def timed(step, args, rank, world, device, audit=False, bucketer=None):
         dist.all_gather(out, t)
         per_rank = [float(o.item()) for o in out]
     info = {"gpu_telemetry": telemetry} if telemetry.get("before") or telemetry.get("after") else {}
+    if dump is not None:
+        info["dump"] = dump
     if host:
         # a host issue time close to the GPU step time means the step is launch / host bound
         # the fastest step's issue time is the host cost of a step whose launches never waited;
@@ -670,6 +723,9 @@ def run_one(build, args, rank, world, device, kind):
     import torch
     step, close, info = build(args, rank, world, device, kind)
     bucketer = info.pop("bucketer", None)
+    if not args.full:
+        bucketer = None                 # the bucket timeline costs a step of its own
+    weights = info.pop("weights")
     prio = None
     if device.type == "cuda" and os.environ.get("CLOUDTIK_AMD_COMPUTE_PRIO", "0") == "1":
         # the step's own stream at the highest priority: the gradient side stream (and RCCL's
@@ -679,10 +735,14 @@ def run_one(build, args, rank, world, device, kind):
         prio.wait_stream(torch.cuda.current_stream())
     with (torch.cuda.stream(prio) if prio is not None else contextlib.nullcontext()):
         elapsed, per_rank, loss, step_ms, audit = timed(step, args, rank, world, device,
-                                                        audit=info["unit"] == "images/s", bucketer=bucketer)
+                                                        audit=args.full and info["unit"] == "images/s",
+                                                        bucketer=bucketer,
+                                                        weights=weights if args.dump_outputs and rank == 0 else None)
+    if audit and "dump" in audit:
+        write_outputs(args.dump_outputs, info["model"], audit.pop("dump"))
     if prio is not None:
         torch.cuda.current_stream().wait_stream(prio)
-    del bucketer
+    del bucketer, weights
     host_ms = audit.pop("host_issue_ms_mean", None) if audit else None
     info["host_issue_ms_min"] = audit.pop("host_issue_ms_min", None) if audit else None
     host_arr = audit.pop("host_ms", None) if audit else None
@@ -732,10 +792,11 @@ def main():
     if args.impl == "native" or args.compare_eager:
         setup_tunableop(args.tunableop, rank)
 
+    # a plain run measures the headline half only; --full adds the ResNet one
     if args.model == "all":
-        kinds = [("bert", "bert-large"), ("resnet", "resnet50")]
+        kinds = [("bert", "bert-large"), ("resnet", "resnet50")][:2 if args.full else 1]
     elif args.model == "tiny":
-        kinds = [("bert", "tiny"), ("resnet", "tiny")]
+        kinds = [("bert", "tiny"), ("resnet", "tiny")][:2 if args.full else 1]
     elif args.model == "resnet50":
         kinds = [("resnet", "resnet50")]
     else:
@@ -748,10 +809,11 @@ def main():
         results.append(r)
     # the stock-PyTorch baseline AFTER every native half (the native numbers are taken on a
     # chip that has not yet run anything else); short unless --compare-eager
-    base_steps = args.baseline_steps if args.baseline_steps >= 0 else (5 if world == 1 else 0)
+    base_steps = args.baseline_steps if args.baseline_steps >= 0 else (5 if world == 1 and args.full else 0)
     if args.impl == "native" and (args.compare_eager or base_steps > 0):
         import copy
         eargs = copy.copy(args)
+        eargs.dump_outputs = None           # the dump is the timed native path's
         if not args.compare_eager:
             eargs.steps, eargs.warmup = base_steps, args.baseline_warmup
         for (fam, kind), r in zip(kinds, results):

@@ -51,6 +51,15 @@ def _creds(cfg: Dict[str, Any], env_id: str, env_secret: str):
     return ak, sk
 
 
+def _huawei_project(cfg: Dict[str, Any]) -> str:
+    """The project id of the region's endpoints: ``provider.project_id``, or like the access
+    key pair from the environment (the reference's example configs name neither)."""
+    project = cfg.get("project_id") or os.environ.get("HUAWEICLOUD_SDK_PROJECT_ID")
+    if not project:
+        raise RuntimeError("no project id: set provider.project_id or HUAWEICLOUD_SDK_PROJECT_ID")
+    return project
+
+
 # ------------------------------------------------------------------------------- Aliyun
 _ECS_VERSION = "2014-05-26"
 
@@ -308,7 +317,7 @@ class HuaweiCloudNodeProvider(NodeProvider):
     def __init__(self, provider_config, cluster_name, transport=None):
         super().__init__(provider_config, cluster_name)
         self.region = provider_config["region"]
-        self.project = provider_config["project_id"]
+        self.project = _huawei_project(provider_config)
         if transport is None and provider_config.get("_transport") is None:
             ak, sk = _creds(provider_config, "HUAWEICLOUD_SDK_AK", "HUAWEICLOUD_SDK_SK")
             transport = huawei_transport(ak, sk)

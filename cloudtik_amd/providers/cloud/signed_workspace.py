@@ -399,11 +399,11 @@ class HuaweiCloudWorkspace:
 
     def __init__(self, provider_config: Dict[str, Any], workspace_name: str, call=None, obs=None,
                  poll_s: float = 3.0, timeout_s: float = 900.0):
-        from cloudtik_amd.providers.cloud.signed_providers import _creds, huawei_transport
+        from cloudtik_amd.providers.cloud.signed_providers import _creds, _huawei_project, huawei_transport
         self.cfg = provider_config
         self.ws = workspace_name
         self.region = provider_config["region"]
-        self.project = provider_config["project_id"]
+        self.project = _huawei_project(provider_config)
         call = call or provider_config.get("_transport")
         if call is None:
             call = huawei_transport(*_creds(provider_config, "HUAWEICLOUD_SDK_AK", "HUAWEICLOUD_SDK_SK"))

@@ -10,7 +10,7 @@ timeout -k 10 300 python -u -m pytest tests/test_conv_igemm.py tests/test_miopen
   --timeout-method thread > "$OUT/tests.txt" 2>&1 || { tail -40 "$OUT/tests.txt"; exit 1; }
 tail -1 "$OUT/tests.txt"
 for arm in 1 0 1; do
-  CLOUDTIK_AMD_CONV_IGEMM=$arm timeout -k 10 300 python -u bench.py --model resnet50 --steps 20 --warmup 5 \
+  CLOUDTIK_AMD_CONV_IGEMM=$arm timeout -k 10 300 python -u bench.py --model resnet50 --full --steps 20 --warmup 5 \
     > "$OUT/bench_igemm$arm.log" 2>&1 || { tail -20 "$OUT/bench_igemm$arm.log"; exit 1; }
   echo "igemm=$arm: $(tail -1 "$OUT/bench_igemm$arm.log" | cut -c1-400)"
   grep "kernel audit" "$OUT/bench_igemm$arm.log" | cut -c1-300

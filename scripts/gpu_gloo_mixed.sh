@@ -9,7 +9,7 @@ mkdir -p "$O"
 cd "$R"
 rc=0
 for i in 1 2 3; do
-  env CLOUDTIK_AMD_STEP_PHASES=${PHASES:-0} ${EXTRA_ENV:-} timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --model all --steps 6 --warmup 2 --batch 64 --rn-batch 64 \
+  env CLOUDTIK_AMD_STEP_PHASES=${PHASES:-0} ${EXTRA_ENV:-} timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --model all --full --steps 6 --warmup 2 --batch 64 --rn-batch 64 \
       > "$O/mixed_$i.log" 2> "$O/mixed_$i.err" || { rc=$?; echo "run $i failed rc=$rc"; tail -5 "$O/mixed_$i.err"; break; }
   python3 - "$O/mixed_$i.log" <<'PY'
 import json, sys

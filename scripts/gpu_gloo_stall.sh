@@ -9,7 +9,7 @@ cd "$R"
 run() { # tag env... -- args
   local tag=$1; shift
   env "$@" timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --steps 8 --warmup 2 --batch 64 --rn-batch 64 \
-      --model "${MODEL:-all}" > "$O/$tag.log" 2> "$O/$tag.err"
+      --model "${MODEL:-all}" --full > "$O/$tag.log" 2> "$O/$tag.err"
 }
 MODEL=resnet50 run rn_only CLOUDTIK_X=1 \
  && run all_side CLOUDTIK_AMD_WGRAD_STREAM=1 \

@@ -4,7 +4,7 @@ set -u
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$R/gpurun_out/gloo_trace"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --hip-trace --output-format csv -d "$OUT/t" -o t -- python3 -u "$R/bench.py" --gpus 2 --dist-backend gloo --model all --steps 6 --warmup 2 --batch 64 --rn-batch 64 > "$OUT/run.log" 2> "$OUT/run.err" || { tail -5 "$OUT/run.err"; exit 1; }
+timeout -k 10 400 rocprofv3 --hip-trace --output-format csv -d "$OUT/t" -o t -- python3 -u "$R/bench.py" --gpus 2 --dist-backend gloo --model all --full --steps 6 --warmup 2 --batch 64 --rn-batch 64 > "$OUT/run.log" 2> "$OUT/run.err" || { tail -5 "$OUT/run.err"; exit 1; }
 python3 - "$OUT/run.log" <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

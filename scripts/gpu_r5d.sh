@@ -9,7 +9,7 @@ cd "$R"
 timeout -k 10 300 python -u -m pytest tests/test_gemm_nt_gpu.py tests/test_model_parity.py -m gpu -x -v --timeout 120 --timeout-method thread > "$O/gemm_tests.txt" 2>&1 \
  && tail -1 "$O/gemm_tests.txt" \
  && bash "$R/scripts/gpu_ab_env.sh" "$TAG/ab" CLOUDTIK_AMD_FFN_STORE_DGELU "0 1" 3 bert-large \
- && timeout -k 10 400 python -u bench.py --gpus 2 --dist-backend gloo --model all --steps 8 --warmup 2 --batch 64 --rn-batch 64 > "$O/gloo_mixed.log" 2> "$O/gloo_mixed.err" \
+ && timeout -k 10 400 python -u bench.py --gpus 2 --dist-backend gloo --model all --full --steps 8 --warmup 2 --batch 64 --rn-batch 64 > "$O/gloo_mixed.log" 2> "$O/gloo_mixed.err" \
  && python - "$O/gloo_mixed.log" <<'PY'
 import json, sys
 d = json.loads([x for x in open(sys.argv[1]) if x.startswith("{")][-1])

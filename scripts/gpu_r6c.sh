@@ -10,7 +10,7 @@ timeout -k 10 300 python -u -m pytest tests/test_ddp_gloo.py tests/test_bucket_r
 tail -1 "$O/ddp_gpu.txt"
 rc=0
 for i in 1 2; do
-  env CLOUDTIK_AMD_STEP_PHASES=50 timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --model all --steps 6 --warmup 2 --batch 64 --rn-batch 64 --baseline-steps 0 \
+  env CLOUDTIK_AMD_STEP_PHASES=50 timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --model all --full --steps 6 --warmup 2 --batch 64 --rn-batch 64 --baseline-steps 0 \
       > "$O/mixed_$i.log" 2> "$O/mixed_$i.err" || { rc=$?; echo "run $i failed rc=$rc"; tail -5 "$O/mixed_$i.err"; break; }
   python3 - "$O/mixed_$i.log" <<'PY'
 import json, sys

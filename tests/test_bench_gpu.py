@@ -17,7 +17,7 @@ def _run(*extra):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--model", "tiny", "--gpus", "2",
-                          "--dist-backend", "gloo", "--steps", "3", "--warmup", "1", *extra],
+                          "--dist-backend", "gloo", "--steps", "3", "--warmup", "1", "--full", *extra],
                          capture_output=True, text=True, env=env, timeout=300, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -9,15 +9,33 @@ import pytest
 from cloudtik_amd.core.config import schema as jschema
 from cloudtik_amd.core.config.instance_templates import available, synthesize
 
-REF = "/root/reference/examples/cluster"
+# the reference's example cluster configs (examples/cluster/**/*.yaml), stored as fixtures
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_examples", "cluster")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference examples not present")
 def test_every_reference_example_cluster_bootstraps(monkeypatch, tmp_path):
+    import sys
+    import types
+    from cloudtik_amd.core import cluster_config
     from cloudtik_amd.core.cluster_config import load_cluster_config
     from cloudtik_amd.providers.cloud import keypairs
-    # no cloud API here: the key-pair step sees a cloud without key pairs and a fresh ~/.ssh
+    # no cloud API here: the key-pair step sees a cloud without key pairs and a ~/.ssh that holds
+    # only the user's own id_rsa pair, which the Azure examples name
     monkeypatch.setenv("HOME", str(tmp_path))
+    (tmp_path / ".ssh").mkdir()
+    (tmp_path / ".ssh" / "id_rsa").write_text("PRIVATE KEY\n")
+    (tmp_path / ".ssh" / "id_rsa.pub").write_text("ssh-rsa AAAAB3NzaC1yc2E= user@host\n")
+    # every config really bootstraps: no bootstrapped copy cached by an earlier run is read back
+    monkeypatch.setattr(cluster_config, "CONFIG_CACHE_DIR", str(tmp_path / "configs"))
+    # the providers are constructed before the key-pair step: the signed-API ones want an access
+    # key pair and a project id (nothing is ever signed with them), the AWS one an SDK client
+    # (never called)
+    for var in ("ALIBABA_CLOUD_ACCESS_KEY_ID", "ALIBABA_CLOUD_ACCESS_KEY_SECRET",
+                "HUAWEICLOUD_SDK_AK", "HUAWEICLOUD_SDK_SK", "HUAWEICLOUD_SDK_PROJECT_ID"):
+        monkeypatch.setenv(var, "test-only")
+    sdk = types.ModuleType("boto3")
+    sdk.client = lambda service, region_name=None: types.SimpleNamespace(service=service, region=region_name)
+    monkeypatch.setitem(sys.modules, "boto3", sdk)
     orig = keypairs.configure_cloud_key_pair
     monkeypatch.setattr(keypairs, "configure_cloud_key_pair",
                         lambda cfg, cloud, region, describe, create: orig(cfg, cloud, region, lambda n: False,

@@ -76,6 +76,9 @@ def _slice(tmp_path, gpu, model_args):
         assert res["n_gpus"] == 1 and math.isfinite(res["final_loss"]) and res["value"] > 0
         return rep, res
     finally:
+        # the head is this host: only the stop commands end its daemons (state server, node monitor,
+        # controller); --hard alone forgets the node and leaves them running
+        _run(env, "stop", cfg, "-y", check=False)
         _run(env, "stop", cfg, "-y", "--hard", check=False)
 
 
