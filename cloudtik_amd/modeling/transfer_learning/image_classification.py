@@ -141,6 +141,25 @@ class ImageClassificationModel:
             x = x.contiguous(memory_format=torch.channels_last)
         return torch.softmax(self.model(x).float(), -1)
 
+    # ---------------------------------------------------------------- quantization
+    # The hot path of this model is the implicit-GEMM convolutions; an int8 convolution does not
+    # exist in the op library yet, so the hooks say so (as the reference's base class does,
+    # modeling/transfer_learning/model.py:107-190).  The text classifier implements them.
+    _NO_INT8 = ("int8 post-training quantization is not implemented for image classification models: "
+                "the op library has no int8 convolution (text_classification models support it)")
+
+    def export_quantization_config(self, config_file_path, dataset, batch_size, overwrite=False, **kwargs):
+        raise NotImplementedError(self._NO_INT8)
+
+    def quantize(self, saved_model_dir, output_dir, config_path, dataset=None):
+        raise NotImplementedError(self._NO_INT8)
+
+    def benchmark(self, saved_model_dir, config_path=None, mode='performance', model_type='fp32', dataset=None):
+        raise NotImplementedError(self._NO_INT8)
+
+    export_neural_compressor_config = export_quantization_config
+    benchmark_neural_compressor = benchmark
+
     # ---------------------------------------------------------------- persistence
     def export(self, output_dir: str) -> str:
         from safetensors.torch import save_file

@@ -19,6 +19,7 @@ from torch.utils.data import DataLoader, Dataset
 from cloudtik_amd.models.bert import BertConfig, BertModel
 
 from .image_classification import _default_device, load_pretrained, load_state_file
+from .quantization import TextQuantizationMixin
 
 ENCODERS = {"bert-large-uncased": BertConfig.large, "bert-base-uncased": BertConfig.base, "bert-tiny": BertConfig.tiny}
 
@@ -35,7 +36,7 @@ class BertClassifier(nn.Module):
         return self.classifier(F.dropout(pooled, self.dropout, self.training))
 
 
-class TextClassificationModel:
+class TextClassificationModel(TextQuantizationMixin):
     use_case = "text_classification"
 
     def __init__(self, model_name: str = "bert-base-uncased", num_classes: int = 2,
@@ -68,6 +69,8 @@ class TextClassificationModel:
               log_every: int = 50, distributed: bool = False, nnodes: int = 1, nproc_per_node: int = 1,
               hosts: Optional[str] = None, hostfile: Optional[str] = None, shared_dir: Optional[str] = None,
               launcher: Optional[str] = None) -> List[Dict[str, float]]:
+        if self.quantization:
+            raise RuntimeError("a quantized model is inference-only; train the float model and quantize again")
         if distributed:
             from cloudtik_amd.modeling.transfer_learning.distributed import fit_distributed
             return fit_distributed(self, dataset, dict(
@@ -101,7 +104,7 @@ class TextClassificationModel:
             _, m = self._step(self.model, b)
             correct += float(m["accuracy"]) * len(b["label"])
             n += len(b["label"])
-        self.model.train()
+        self.model.train(not self.quantization)
         return {"accuracy": correct / max(n, 1)}
 
     @torch.no_grad()
@@ -115,8 +118,11 @@ class TextClassificationModel:
         path = os.path.join(output_dir, "model.safetensors")
         save_file({k: v.detach().contiguous().cpu() for k, v in self.model.state_dict().items()}, path)
         with open(os.path.join(output_dir, "model_config.json"), "w") as f:
-            json.dump({"use_case": self.use_case, "model_name": self.model_name, "num_classes": self.num_classes,
-                       "classes": self.classes, "bert": self.cfg.to_dict()}, f)
+            cfg = {"use_case": self.use_case, "model_name": self.model_name, "num_classes": self.num_classes,
+                   "classes": self.classes, "bert": self.cfg.to_dict()}
+            if self.quantization:                      # an int8 model (quantization.py)
+                cfg["quantization"] = self.quantization
+            json.dump(cfg, f)
         return path
 
     @classmethod
@@ -126,5 +132,11 @@ class TextClassificationModel:
         overrides = {k: v for k, v in cfg["bert"].items()}
         m = cls(cfg["model_name"], cfg["num_classes"], device=device, classes=cfg["classes"], **overrides)
         sd = load_state_file(os.path.join(output_dir, "model.safetensors"))
-        m.model.load_state_dict({k: v.to(m.dtype) if v.is_floating_point() else v for k, v in sd.items()})
+        if cfg.get("quantization"):                    # written by quantize(): int8 encoder linears
+            from cloudtik_amd.models.bert_quant import QuantBertClassifier
+            m.quantization = cfg["quantization"]
+            m.model = QuantBertClassifier(m.cfg, m.num_classes, m.quantization["sites"], device=m.device,
+                                          dtype=m.dtype)
+        keep = lambda k, v: not v.is_floating_point() or k.endswith("_weight_scale")   # int8 / fp32 scales
+        m.model.load_state_dict({k: v if keep(k, v) else v.to(m.dtype) for k, v in sd.items()})
         return m

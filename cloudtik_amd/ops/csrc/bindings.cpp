@@ -824,6 +824,7 @@ void register_deform(pybind11::module& m); // bindings_deform.cpp
 void register_p2p(pybind11::module& m);    // bindings_p2p.cpp
 void register_lt(pybind11::module& m);     // bindings_lt.cpp
 void register_conv(pybind11::module& m);   // bindings_conv.cpp
+void register_quant(pybind11::module& m);  // bindings_quant.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "cloudtik_amd CDNA4 (gfx950) op library";
@@ -833,6 +834,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_p2p(m);
   register_lt(m);
   register_conv(m);
+  register_quant(m);
   m.def("maxpool3s2_bwd_bn", &maxpool3s2_bwd_bn);
   m.def("bn_fwd_train_given2", &bn_fwd_train_given2);
   m.def("bn_bwd_given_pair", &bn_bwd_given_pair);

@@ -1,0 +1,94 @@
+// Bindings for the int8 quantization kernels (quant.hip).  Every constraint the kernels rely
+// on (dtype, contiguity, 16-byte alignment, K / N multiples, K range, matching sizes) is
+// checked here; a violated one raises and nothing is launched.
+#include <torch/extension.h>
+#include <ATen/hip/HIPContext.h>
+#include <hip/hip_runtime.h>
+
+extern "C" {
+int ct_quant_rows_i8(const void*, void*, float*, int, int, hipStream_t);
+int ct_gemm_i8_nt(const void*, const void*, const float*, const float*, const void*, void*, int, int, int, int,
+                  hipStream_t);
+}
+
+namespace {
+
+#define QCHECK(x) TORCH_CHECK((x).is_cuda() && (x).is_contiguous(), #x " must be a contiguous GPU tensor")
+#define QDT(x, d, name) TORCH_CHECK((x).scalar_type() == (d), #x " must be " name)
+#define QALIGN(x) TORCH_CHECK(reinterpret_cast<uintptr_t>((x).data_ptr()) % 16 == 0, #x " must be 16-byte aligned")
+
+hipStream_t stream() { return at::hip::getCurrentHIPStream().stream(); }
+
+// x bf16 [..., K] -> (q int8 [..., K], scale fp32 [...])
+std::vector<at::Tensor> quant_rows_i8(at::Tensor x) {
+  QCHECK(x); QDT(x, at::kBFloat16, "bf16"); QALIGN(x);
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "quant_rows_i8: empty input");
+  const int64_t K = x.size(-1), M = x.numel() / K;
+  TORCH_CHECK(K % 16 == 0 && K <= 8192, "quant_rows_i8: K must be a multiple of 16 and <= 8192, got ", K);
+  TORCH_CHECK(M <= INT32_MAX, "quant_rows_i8: too many rows");
+  auto q = at::empty(x.sizes(), x.options().dtype(at::kChar));
+  auto lead = x.sizes().vec();
+  lead.pop_back();
+  auto scale = at::empty(lead, x.options().dtype(at::kFloat));
+  int rc = ct_quant_rows_i8(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), (int)M, (int)K, stream());
+  TORCH_CHECK(rc == 0, "ct_quant_rows_i8 failed: ", rc);
+  return {q, scale};
+}
+
+// shapes of an NT int8 product: a_q [M, K], w_q [N, K], out [M, N]
+void check_operands(const at::Tensor& a_q, const at::Tensor& w_q, const at::Tensor& out, int64_t& M, int64_t& N,
+                    int64_t& K) {
+  QCHECK(a_q); QCHECK(w_q); QCHECK(out);
+  QDT(a_q, at::kChar, "int8"); QDT(w_q, at::kChar, "int8");
+  QALIGN(a_q); QALIGN(w_q); QALIGN(out);
+  TORCH_CHECK(a_q.dim() == 2 && w_q.dim() == 2 && out.dim() == 2, "gemm_i8_nt: operands must be 2-D");
+  M = a_q.size(0); K = a_q.size(1); N = w_q.size(0);
+  TORCH_CHECK(w_q.size(1) == K, "gemm_i8_nt: a_q [M, K] and w_q [N, K] disagree on K");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == N, "gemm_i8_nt: out must be [M, N]");
+  TORCH_CHECK(M >= 1 && M <= 65535 * 128, "gemm_i8_nt: M out of range");
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= 8192, "gemm_i8_nt: K must be a multiple of 64 and <= 8192, got ", K);
+  TORCH_CHECK(N >= 64 && N % 64 == 0, "gemm_i8_nt: N must be a multiple of 64, got ", N);
+  TORCH_CHECK(M * N <= (int64_t)INT32_MAX * 64, "gemm_i8_nt: output too large");
+}
+
+// out bf16 [M, N] = act((a_q . w_q^T) * a_scale[m] * w_scale[n] + bias[n]); act 0 none, 1 GELU
+void gemm_i8_nt(at::Tensor a_q, at::Tensor a_scale, at::Tensor w_q, at::Tensor w_scale,
+                c10::optional<at::Tensor> bias, int64_t act, at::Tensor out) {
+  int64_t M, N, K;
+  check_operands(a_q, w_q, out, M, N, K);
+  QDT(out, at::kBFloat16, "bf16");
+  QCHECK(a_scale); QCHECK(w_scale);
+  QDT(a_scale, at::kFloat, "fp32"); QDT(w_scale, at::kFloat, "fp32");
+  QALIGN(w_scale);
+  TORCH_CHECK(a_scale.numel() == M && w_scale.numel() == N, "gemm_i8_nt: scales must be [M] and [N]");
+  TORCH_CHECK(act == 0 || act == 1, "gemm_i8_nt: act must be 0 (none) or 1 (GELU)");
+  const void* b = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    QCHECK(*bias); QDT(*bias, at::kBFloat16, "bf16");
+    TORCH_CHECK(bias->numel() == N, "gemm_i8_nt: bias must be [N]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(bias->data_ptr()) % 8 == 0, "bias must be 8-byte aligned");
+    b = bias->data_ptr();
+  }
+  int rc = ct_gemm_i8_nt(a_q.data_ptr(), w_q.data_ptr(), a_scale.data_ptr<float>(), w_scale.data_ptr<float>(), b,
+                         out.data_ptr(), (int)M, (int)N, (int)K, (int)act, stream());
+  TORCH_CHECK(rc == 0, "ct_gemm_i8_nt failed: ", rc);
+}
+
+// out int32 [M, N] = a_q . w_q^T, the exact accumulators
+void gemm_i8_nt_raw(at::Tensor a_q, at::Tensor w_q, at::Tensor out) {
+  int64_t M, N, K;
+  check_operands(a_q, w_q, out, M, N, K);
+  QDT(out, at::kInt, "int32");
+  int rc = ct_gemm_i8_nt(a_q.data_ptr(), w_q.data_ptr(), nullptr, nullptr, nullptr, out.data_ptr(), (int)M, (int)N,
+                         (int)K, 2, stream());
+  TORCH_CHECK(rc == 0, "ct_gemm_i8_nt failed: ", rc);
+}
+
+}  // namespace
+
+void register_quant(pybind11::module& m) {
+  m.def("quant_rows_i8", &quant_rows_i8);
+  m.def("gemm_i8_nt", &gemm_i8_nt, pybind11::arg("a_q"), pybind11::arg("a_scale"), pybind11::arg("w_q"),
+        pybind11::arg("w_scale"), pybind11::arg("bias"), pybind11::arg("act"), pybind11::arg("out"));
+  m.def("gemm_i8_nt_raw", &gemm_i8_nt_raw);
+}

@@ -159,3 +159,41 @@ def attention(q, k, v, key_bias=None, p=0.0, seed=0, offset=0, scale=None, causa
         keep = attn_dropout_keep(*s.shape, p, seed, offset).to(s.device)
         pr = torch.where(keep, pr / (1.0 - p), torch.zeros_like(pr))
     return torch.matmul(pr, v.float()).to(q.dtype)
+
+
+# ------------------------------------------------------------------ int8 quantization
+def quantize_rows(x):
+    """Symmetric per-row int8 quantization, the arithmetic of csrc/quant.hip: amax over the last
+    dimension in fp32, scale = amax / 127, q = clamp(rne(x * (127 / amax)), -127, 127) with one
+    fp32 multiply; an all-zero row gives scale 0 and q 0.  Returns (q int8, scale fp32)."""
+    xf = x.float()
+    amax = xf.abs().amax(-1, keepdim=True)
+    # tensor / tensor: one IEEE division each (``127.0 / amax`` is reciprocal-then-multiply in
+    # PyTorch, two roundings; a tensor divided by a Python scalar is too on some devices)
+    c127 = torch.full_like(amax, 127.0)
+    scale = amax / c127
+    inv = torch.where(amax > 0, c127 / amax, torch.zeros_like(amax))
+    q = torch.clamp(torch.round(xf * inv), -127.0, 127.0).to(torch.int8)
+    return q, scale.squeeze(-1)
+
+
+def gemm_i8_nt_raw(a_q, w_q):
+    """The exact int32 accumulators of a_q [M, K] . w_q [N, K]^T."""
+    return torch.matmul(a_q.to(torch.int32), w_q.to(torch.int32).t())
+
+
+def dequant_epilogue(acc, a_scale, w_scale, bias=None, act=ACT_NONE, dtype=torch.float32):
+    """y = act(acc * (a_scale[m] * w_scale[n]) + bias[n]) in fp32, rounded to ``dtype``."""
+    y = acc.to(torch.float32) * (a_scale.float().unsqueeze(-1) * w_scale.float().unsqueeze(0))
+    if bias is not None:
+        y = y + bias.float()
+    if act == ACT_GELU:
+        y = F.gelu(y)
+    elif act != ACT_NONE:
+        raise ValueError(f"linear_i8: unsupported activation {act}")
+    return y.to(dtype)
+
+
+def linear_i8(a_q, a_scale, w_q, w_scale, bias=None, act=ACT_NONE, dtype=torch.float32):
+    """a_q [M, K] int8 with per-row scales against w_q [N, K] int8 with per-channel scales."""
+    return dequant_epilogue(gemm_i8_nt_raw(a_q, w_q), a_scale, w_scale, bias, act, dtype)
