@@ -7,6 +7,12 @@ Here the approach ``post_training_dynamic_quant`` -- int8 weights, activations q
 call -- runs through the in-tree HIP kernels (``ops.quant``, ``models.bert_quant``).  The tuning
 loop is a short ladder of site sets instead of INC's search: a trial is accepted when its
 relative accuracy loss on the evaluation dataset is within the configured criterion.
+
+``post_training_static_quant`` keeps the int8 weights and replaces the per-token activation
+scales by one range per site and layer, calibrated on the first ``sampling_size`` examples of the
+dataset (``models.bert_quant.calibrate``).  The ranges are written into the quantization block of
+``model_config.json``; with them the int8 activations come straight out of the LayerNorm and GEMM
+epilogues instead of separate quantize passes.
 """
 from __future__ import annotations
 
@@ -18,6 +24,8 @@ from typing import Dict, List, Optional
 import torch
 
 APPROACH = "post_training_dynamic_quant"
+STATIC_APPROACH = "post_training_static_quant"
+APPROACHES = (APPROACH, STATIC_APPROACH)
 
 # the trial ladder: all four linears; then without ffn2 (the largest K, fed by the post-GELU
 # tensor); then the two linears whose inputs are LayerNorm outputs
@@ -29,7 +37,8 @@ def _bad_int(v, lowest):
 
 
 def build_config(model_name: str, dataset, batch_size: int, accuracy_criterion_relative, exit_policy_timeout,
-                 exit_policy_max_trials, tuning_random_seed, tuning_workspace) -> dict:
+                 exit_policy_max_trials, tuning_random_seed, tuning_workspace, approach=APPROACH,
+                 calibration_sampling_size=100) -> dict:
     loader = lambda: {"batch_size": batch_size,
                       "dataset": {"text_classification": {"num_examples": len(dataset),
                                                           "max_length": int(dataset.ids.shape[1])}}}
@@ -38,9 +47,12 @@ def build_config(model_name: str, dataset, batch_size: int, accuracy_criterion_r
               "random_seed": tuning_random_seed}
     if tuning_workspace:
         tuning["workspace"] = {"path": tuning_workspace}
+    quantization = {"approach": approach}
+    if approach == STATIC_APPROACH:
+        quantization["calibration"] = {"sampling_size": calibration_sampling_size}
     return {"version": 1.0,
             "model": {"name": model_name, "framework": "cloudtik_amd"},
-            "quantization": {"approach": APPROACH},
+            "quantization": quantization,
             "evaluation": {"accuracy": {"metric": {"topk": 1}, "dataloader": loader()},
                            "performance": {"configs": {"num_of_instance": 1}, "dataloader": loader()}},
             "tuning": tuning}
@@ -51,9 +63,17 @@ def read_config(path: str) -> dict:
     with open(path) as f:
         cfg = yaml.safe_load(f) or {}
     approach = cfg.get("quantization", {}).get("approach")
-    if approach != APPROACH:
-        raise ValueError(f"unsupported quantization approach {approach!r}; this library implements {APPROACH!r}")
+    if approach not in APPROACHES:
+        raise ValueError(f"unsupported quantization approach {approach!r}; this library implements "
+                         f"{' and '.join(map(repr, APPROACHES))}")
     return cfg
+
+
+def _sampling_size(cfg: dict) -> int:
+    n = cfg.get("quantization", {}).get("calibration", {}).get("sampling_size", 100)
+    if _bad_int(n, 1) or isinstance(n, bool):
+        raise ValueError(f"Invalid calibration sampling size ({n}) in the config. Expected a positive integer.")
+    return n
 
 
 def _batch_size(cfg: dict, section: str, default: int) -> int:
@@ -69,8 +89,11 @@ class TextQuantizationMixin:
     # ------------------------------------------------------------------ config
     def export_quantization_config(self, config_file_path, dataset, batch_size, overwrite=False,
                                    accuracy_criterion_relative=0.01, exit_policy_timeout=0,
-                                   exit_policy_max_trials=50, tuning_random_seed=9527, tuning_workspace=''):
+                                   exit_policy_max_trials=50, tuning_random_seed=9527, tuning_workspace='',
+                                   approach=APPROACH, calibration_sampling_size=100):
         """Write the quantization / tuning config (YAML) for ``quantize`` and ``benchmark``.
+        ``approach`` is ``post_training_dynamic_quant`` or ``post_training_static_quant``; the
+        static one calibrates on the first ``calibration_sampling_size`` examples.
 
         Raises FileExistsError when the file exists and ``overwrite`` is False, NotImplementedError
         for a dataset that is not a ``TextClassificationDataset``, ValueError for a parameter
@@ -99,10 +122,16 @@ class TextQuantizationMixin:
                              "Expected a positive integer.")
         if not isinstance(tuning_workspace, str):
             raise ValueError("Invalid value for the tuning workspace directory. Expected a string.")
+        if approach not in APPROACHES:
+            raise ValueError(f"Invalid value for the approach ({approach!r}). Expected one of {list(APPROACHES)}.")
+        if _bad_int(calibration_sampling_size, 1) or isinstance(calibration_sampling_size, bool):
+            raise ValueError(f"Invalid value for the calibration sampling size ({calibration_sampling_size}). "
+                             "Expected a positive integer.")
         if not tuning_workspace and os.getenv("OUTPUT_DIR", ""):
             tuning_workspace = os.path.join(os.environ["OUTPUT_DIR"], "nc_workspace")
         cfg = build_config(self.model_name, dataset, batch_size, accuracy_criterion_relative, exit_policy_timeout,
-                           exit_policy_max_trials, tuning_random_seed, tuning_workspace)
+                           exit_policy_max_trials, tuning_random_seed, tuning_workspace, approach,
+                           calibration_sampling_size)
         import yaml
         parent = os.path.dirname(config_file_path)
         if parent:
@@ -113,15 +142,16 @@ class TextQuantizationMixin:
     def export_neural_compressor_config(self, config_file_path, dataset, batch_size, overwrite=False,
                                         resize_interpolation='bicubic', accuracy_criterion_relative=0.01,
                                         exit_policy_timeout=0, exit_policy_max_trials=50, tuning_random_seed=9527,
-                                        tuning_workspace=''):
+                                        tuning_workspace='', approach=APPROACH, calibration_sampling_size=100):
         """The reference's name and signature (``resize_interpolation`` is validated and unused,
-        as for the reference's text models)."""
+        as for the reference's text models), then ``approach`` and ``calibration_sampling_size``."""
         if resize_interpolation not in ('bilinear', 'nearest', 'bicubic'):
             raise ValueError(f"Invalid value for resize interpolation ({resize_interpolation}). Expected one of "
                              "the following values: bilinear, nearest, bicubic")
         return self.export_quantization_config(config_file_path, dataset, batch_size, overwrite,
                                                accuracy_criterion_relative, exit_policy_timeout,
-                                               exit_policy_max_trials, tuning_random_seed, tuning_workspace)
+                                               exit_policy_max_trials, tuning_random_seed, tuning_workspace,
+                                               approach, calibration_sampling_size)
 
     # ------------------------------------------------------------------ quantize
     def _trial_accuracy(self, wrapper, dataset, batch_size: int) -> float:
@@ -136,9 +166,14 @@ class TextQuantizationMixin:
         the exit policy's trial count / timeout.  Returns the written ``model.safetensors`` path,
         or None -- with nothing written -- when no trial met the criterion.
 
+        A ``post_training_static_quant`` config needs the ``dataset``: the float model is run once
+        over its first ``sampling_size`` examples to calibrate the activation ranges, which every
+        trial then shares.
+
         Raises NotADirectoryError (``saved_model_dir``), FileNotFoundError (its model file, or the
-        config), FileExistsError (``output_dir`` already holds a model)."""
-        from cloudtik_amd.models.bert_quant import QuantBertClassifier
+        config), FileExistsError (``output_dir`` already holds a model), ValueError (a static
+        config without a dataset)."""
+        from cloudtik_amd.models import bert_quant
         if not os.path.isdir(saved_model_dir):
             raise NotADirectoryError(f"The saved model directory ({saved_model_dir}) does not exist.")
         if not os.path.isfile(os.path.join(saved_model_dir, "model.safetensors")):
@@ -150,6 +185,10 @@ class TextQuantizationMixin:
         if os.path.exists(out_model):
             raise FileExistsError(f"A saved model already exists at: {out_model}")
         cfg = read_config(config_path)
+        approach = cfg["quantization"]["approach"]
+        static = approach == STATIC_APPROACH
+        if static and dataset is None:
+            raise ValueError(f"{STATIC_APPROACH} calibrates the activation ranges on a dataset; none was given")
         tuning = cfg.get("tuning", {})
         criterion = float(tuning.get("accuracy_criterion", {}).get("relative", 0.01))
         policy = tuning.get("exit_policy", {})
@@ -161,13 +200,18 @@ class TextQuantizationMixin:
         if fp.quantization:
             raise ValueError(f"the model at {saved_model_dir} is already quantized")
         acc_fp = self._trial_accuracy(fp, dataset, bs) if dataset is not None else None
+        act_amax, calibration = None, None
+        if static:                                        # once, on the float model; the trials share it
+            n = min(_sampling_size(cfg), len(dataset))
+            act_amax = bert_quant.calibrate(fp.model, _calibration_batches(dataset, n, bs))
+            calibration = {"sampling_size": _sampling_size(cfg), "num_examples": n}
         t0, chosen, history = time.monotonic(), None, []
         for trial, sites in enumerate(TRIALS[:max_trials], 1):
             if trial > 1 and timeout and time.monotonic() - t0 > timeout:
                 break
             q = type(self).load(saved_model_dir, device=self.device)
-            q.model = QuantBertClassifier.from_float(q.model, sites)
-            q.quantization = {"approach": APPROACH}
+            q.model = bert_quant.QuantBertClassifier.from_float(q.model, sites, act_amax=act_amax)
+            q.quantization = {"approach": approach}
             acc_q = self._trial_accuracy(q, dataset, bs) if dataset is not None else None
             loss = None
             if acc_q is not None:
@@ -179,9 +223,11 @@ class TextQuantizationMixin:
         if chosen is None:
             return None
         trial, q, acc_q = chosen
-        q.quantization = {"approach": APPROACH, "sites": q.model.sites_per_layer,
-                          "accuracy": {"fp32": acc_fp, "int8": acc_q},
-                          "accuracy_criterion_relative": criterion, "trial": trial, "trials": history}
+        q.quantization = {"approach": approach, "sites": q.model.sites_per_layer}
+        if static:
+            q.quantization.update(act_amax=act_amax, calibration=calibration)
+        q.quantization.update({"accuracy": {"fp32": acc_fp, "int8": acc_q},
+                               "accuracy_criterion_relative": criterion, "trial": trial, "trials": history})
         os.makedirs(output_dir, exist_ok=True)
         return q.export(output_dir)
 
@@ -219,6 +265,12 @@ class TextQuantizationMixin:
     def benchmark_neural_compressor(self, saved_model_dir, inc_config_path, mode='performance', model_type='fp32'):
         """The reference's name and signature."""
         return self.benchmark(saved_model_dir, inc_config_path, mode=mode, model_type=model_type)
+
+
+def _calibration_batches(dataset, n: int, batch_size: int):
+    """The first ``n`` examples of ``dataset`` in order, ``batch_size`` at a time."""
+    from torch.utils.data import DataLoader, Subset
+    return DataLoader(Subset(dataset, range(n)), batch_size=batch_size)
 
 
 @torch.no_grad()

@@ -136,7 +136,7 @@ class TextClassificationModel(TextQuantizationMixin):
             from cloudtik_amd.models.bert_quant import QuantBertClassifier
             m.quantization = cfg["quantization"]
             m.model = QuantBertClassifier(m.cfg, m.num_classes, m.quantization["sites"], device=m.device,
-                                          dtype=m.dtype)
+                                          dtype=m.dtype, act_amax=m.quantization.get("act_amax"))
         keep = lambda k, v: not v.is_floating_point() or k.endswith("_weight_scale")   # int8 / fp32 scales
         m.model.load_state_dict({k: v if keep(k, v) else v.to(m.dtype) for k, v in sd.items()})
         return m

@@ -4,11 +4,17 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
+#include <cmath>
 
 extern "C" {
 int ct_quant_rows_i8(const void*, void*, float*, int, int, hipStream_t);
 int ct_gemm_i8_nt(const void*, const void*, const float*, const float*, const void*, void*, int, int, int, int,
                   hipStream_t);
+int ct_quant_static_i8(const void*, void*, long, float, hipStream_t);
+int ct_layernorm_quant_i8(const void*, const void*, const void*, const void*, const void*, void*, void*, int, int,
+                          float, float, hipStream_t);
+int ct_gemm_i8_nt_static(const void*, const void*, float, const float*, const void*, void*, int, int, int, int, int,
+                         float, hipStream_t);
 }
 
 namespace {
@@ -84,9 +90,93 @@ void gemm_i8_nt_raw(at::Tensor a_q, at::Tensor w_q, at::Tensor out) {
   TORCH_CHECK(rc == 0, "ct_gemm_i8_nt failed: ", rc);
 }
 
+// ------------------------------------------------------------------ static quantization
+// A by-value scale / inverse scale computed on the host from a calibrated range: finite, >= 0,
+// and exactly representable in fp32 (the kernels take a float).
+float checked_factor(double v, const char* name) {
+  TORCH_CHECK(std::isfinite(v) && v >= 0.0, name, " must be finite and non-negative, got ", v);
+  TORCH_CHECK((double)(float)v == v, name, " must be an fp32 value, got ", v);
+  return (float)v;
+}
+
+const void* optional_bf16(const c10::optional<at::Tensor>& t, int64_t numel, size_t align, const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous(), name, " must be a contiguous GPU tensor");
+  TORCH_CHECK(t->scalar_type() == at::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t->numel() == numel, name, " has the wrong size");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % align == 0, name, " must be ", align, "-byte aligned");
+  return t->data_ptr();
+}
+
+// x bf16 [...] -> q int8 [...], q = clamp(rne(x * inv), -127, 127)
+at::Tensor quant_static_i8(at::Tensor x, double inv) {
+  QCHECK(x); QDT(x, at::kBFloat16, "bf16"); QALIGN(x);
+  const float finv = checked_factor(inv, "quant_static_i8: inv");
+  const int64_t n = x.numel();
+  TORCH_CHECK(n > 0, "quant_static_i8: empty input");
+  TORCH_CHECK(n % 16 == 0 && n / 16 <= INT32_MAX, "quant_static_i8: the element count must be a multiple of 16, got ",
+              n);
+  auto q = at::empty(x.sizes(), x.options().dtype(at::kChar));
+  int rc = ct_quant_static_i8(x.data_ptr(), q.data_ptr(), (long)n, finv, stream());
+  TORCH_CHECK(rc == 0, "ct_quant_static_i8 failed: ", rc);
+  return q;
+}
+
+// (y bf16, q int8 or None) = LN(res + (x + bias)) * gamma + beta and its quantization with inv;
+// emit_q false writes y alone
+std::vector<c10::optional<at::Tensor>> layernorm_quant_i8(at::Tensor x, c10::optional<at::Tensor> bias,
+                                                          c10::optional<at::Tensor> res, at::Tensor gamma,
+                                                          c10::optional<at::Tensor> beta, double eps, double inv,
+                                                          bool emit_q) {
+  QCHECK(x); QDT(x, at::kBFloat16, "bf16"); QALIGN(x);
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "layernorm_quant_i8: empty input");
+  const int64_t N = x.size(-1), M = x.numel() / N;
+  TORCH_CHECK(N % 8 == 0 && N <= 2048, "layernorm_quant_i8: N must be a multiple of 8 and <= 2048, got ", N);
+  TORCH_CHECK(M <= INT32_MAX, "layernorm_quant_i8: too many rows");
+  TORCH_CHECK(std::isfinite(eps) && eps >= 0.0, "layernorm_quant_i8: eps must be finite and non-negative");
+  const float finv = checked_factor(inv, "layernorm_quant_i8: inv");
+  const void* g = optional_bf16(gamma, N, 16, "gamma");
+  const void* bi = optional_bf16(bias, N, 16, "bias");
+  const void* be = optional_bf16(beta, N, 16, "beta");
+  const void* r = optional_bf16(res, x.numel(), 16, "residual");
+  auto y = at::empty_like(x);
+  c10::optional<at::Tensor> q;
+  if (emit_q) q = at::empty(x.sizes(), x.options().dtype(at::kChar));
+  int rc = ct_layernorm_quant_i8(x.data_ptr(), bi, r, g, be, y.data_ptr(), emit_q ? q->data_ptr() : nullptr, (int)M,
+                                 (int)N, (float)eps, finv, stream());
+  TORCH_CHECK(rc == 0, "ct_layernorm_quant_i8 failed: ", rc);
+  return {y, q};
+}
+
+// out [M, N] = act((a_q . w_q^T) * a_scale * w_scale[n] + bias[n]) with ONE activation scale; a bf16
+// out takes the result, an int8 out its quantization with out_inv
+void gemm_i8_nt_static(at::Tensor a_q, double a_scale, at::Tensor w_q, at::Tensor w_scale,
+                       c10::optional<at::Tensor> bias, int64_t act, at::Tensor out, double out_inv) {
+  int64_t M, N, K;
+  check_operands(a_q, w_q, out, M, N, K);
+  const bool i8 = out.scalar_type() == at::kChar;
+  TORCH_CHECK(i8 || out.scalar_type() == at::kBFloat16, "gemm_i8_nt_static: out must be bf16 or int8");
+  QCHECK(w_scale); QDT(w_scale, at::kFloat, "fp32"); QALIGN(w_scale);
+  TORCH_CHECK(w_scale.numel() == N, "gemm_i8_nt_static: w_scale must be [N]");
+  TORCH_CHECK(act == 0 || act == 1, "gemm_i8_nt_static: act must be 0 (none) or 1 (GELU)");
+  const float sa = checked_factor(a_scale, "gemm_i8_nt_static: a_scale");
+  const float inv = checked_factor(out_inv, "gemm_i8_nt_static: out_inv");
+  const void* b = optional_bf16(bias, N, 8, "bias");
+  int rc = ct_gemm_i8_nt_static(a_q.data_ptr(), w_q.data_ptr(), sa, w_scale.data_ptr<float>(), b, out.data_ptr(),
+                                (int)M, (int)N, (int)K, (int)act, i8 ? 1 : 0, inv, stream());
+  TORCH_CHECK(rc == 0, "ct_gemm_i8_nt_static failed: ", rc);
+}
+
 }  // namespace
 
 void register_quant(pybind11::module& m) {
+  m.def("quant_static_i8", &quant_static_i8, pybind11::arg("x"), pybind11::arg("inv"));
+  m.def("layernorm_quant_i8", &layernorm_quant_i8, pybind11::arg("x"), pybind11::arg("bias"),
+        pybind11::arg("residual"), pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("eps"),
+        pybind11::arg("inv"), pybind11::arg("emit_q"));
+  m.def("gemm_i8_nt_static", &gemm_i8_nt_static, pybind11::arg("a_q"), pybind11::arg("a_scale"),
+        pybind11::arg("w_q"), pybind11::arg("w_scale"), pybind11::arg("bias"), pybind11::arg("act"),
+        pybind11::arg("out"), pybind11::arg("out_inv"));
   m.def("quant_rows_i8", &quant_rows_i8);
   m.def("gemm_i8_nt", &gemm_i8_nt, pybind11::arg("a_q"), pybind11::arg("a_scale"), pybind11::arg("w_q"),
         pybind11::arg("w_scale"), pybind11::arg("bias"), pybind11::arg("act"), pybind11::arg("out"));

@@ -6,6 +6,10 @@ computed per call, weights one per output channel, computed once offline.  The r
 is fixed (``reference.quantize_rows``), so the GPU kernel and the CPU reference agree bit for
 bit on the quantized tensors, and the int32 accumulation is exact on both.
 
+Static quantization (``quantize_static``, ``layer_norm_quant``, ``linear_i8_static``) applies the
+same rule against one calibrated range per tensor, so the cast is elementwise and fused into
+the kernel that produces the tensor.
+
 GPU tensors go to the HIP kernels (required; shapes outside their tiling raise), CPU tensors
 to ``ops.reference``.
 """
@@ -74,4 +78,62 @@ def linear_i8(x: Union[torch.Tensor, Quantized], w_q: torch.Tensor, w_scale: tor
         _pkg().require_native().gemm_i8_nt(a2.contiguous(), s1.contiguous(), w_q, w_scale, bias, int(act), out)
     else:
         out = ref.linear_i8(a2, s1, w_q, w_scale, bias, act, dtype or torch.float32)
+    return out.view(*lead, N)
+
+
+# ------------------------------------------------------------------ static (calibrated) ranges
+# One fp32 range ``amax`` per site in place of the per-row maximum.  ``amax`` is a Python float:
+# scale and inv are computed on the host (``reference.static_scales``) and reach the kernels by
+# value, so nothing here reads a device scalar or synchronises.
+def quantize_static(x: torch.Tensor, amax: float) -> torch.Tensor:
+    """x [...] -> q int8 [...], q = clamp(rne(x * (127 / amax)), -127, 127); x ~= q * amax / 127."""
+    _, inv = ref.static_scales(amax)
+    if _pkg()._use_native(x):
+        if x.dtype != torch.bfloat16:
+            raise TypeError(f"quantize_static: GPU input must be bf16, got {x.dtype}")
+        return _pkg().require_native().quant_static_i8(x.contiguous(), inv)
+    return ref.quantize_static(x, amax)
+
+
+def layer_norm_quant(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor] = None, eps: float = 1e-12,
+                     bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                     amax: Optional[float] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Inference LayerNorm that also emits its output quantized against ``amax``:
+    y = LN(residual + (x + bias)) * gamma + beta, q = quantize_static(y, amax).  Returns (y, q);
+    q is None when ``amax`` is None (the int8 output is switched off)."""
+    inv = 0.0 if amax is None else ref.static_scales(amax)[1]
+    if _pkg()._use_native(x):
+        if x.dtype != torch.bfloat16:
+            raise TypeError(f"layer_norm_quant: GPU input must be bf16, got {x.dtype}")
+        y, q = _pkg().require_native().layernorm_quant_i8(
+            x.contiguous(), bias, residual.contiguous() if residual is not None else None, gamma, beta,
+            float(eps), inv, amax is not None)
+        return y, q
+    y, _ = ref.layer_norm(x, gamma, beta, eps, bias, residual)
+    return y, (None if amax is None else ref.quantize_static(y, amax))
+
+
+def linear_i8_static(x: torch.Tensor, a_amax: float, w_q: torch.Tensor, w_scale: torch.Tensor,
+                     bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, out_amax: Optional[float] = None,
+                     dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``linear_i8`` with the calibrated activation range ``a_amax``.  ``x`` [..., K] is floating
+    (quantized here) or already int8.  With ``out_amax`` the result -- rounded to ``dtype`` first
+    -- comes back as int8 quantized against that range, ready for the next int8 linear."""
+    if act not in (ACT_NONE, ACT_GELU):
+        raise ValueError(f"linear_i8_static: act must be ACT_NONE or ACT_GELU, got {act}")
+    a_scale, _ = ref.static_scales(a_amax)
+    out_inv = 0.0 if out_amax is None else ref.static_scales(out_amax)[1]
+    if x.dtype != torch.int8:
+        if dtype is None:
+            dtype = x.dtype
+        x = quantize_static(x, a_amax)
+    lead, K, N = x.shape[:-1], x.shape[-1], w_q.shape[0]
+    a2 = x.reshape(-1, K)
+    if _pkg()._use_native(x, w_q):
+        if dtype not in (None, torch.bfloat16):
+            raise TypeError(f"linear_i8_static: the GPU kernel computes bf16, not {dtype}")
+        out = torch.empty(a2.shape[0], N, device=x.device, dtype=torch.bfloat16 if out_amax is None else torch.int8)
+        _pkg().require_native().gemm_i8_nt_static(a2.contiguous(), a_scale, w_q, w_scale, bias, int(act), out, out_inv)
+    else:
+        out = ref.linear_i8_static(a2, a_amax, w_q, w_scale, bias, act, out_amax, dtype or torch.float32)
     return out.view(*lead, N)

@@ -197,3 +197,45 @@ def dequant_epilogue(acc, a_scale, w_scale, bias=None, act=ACT_NONE, dtype=torch
 def linear_i8(a_q, a_scale, w_q, w_scale, bias=None, act=ACT_NONE, dtype=torch.float32):
     """a_q [M, K] int8 with per-row scales against w_q [N, K] int8 with per-channel scales."""
     return dequant_epilogue(gemm_i8_nt_raw(a_q, w_q), a_scale, w_scale, bias, act, dtype)
+
+
+# ------------------------------------------------------------------ static int8 quantization
+def _check_amax(amax) -> float:
+    amax = float(amax)
+    if not (0.0 <= amax < float("inf")):
+        raise ValueError(f"a quantization range must be finite and non-negative, got {amax}")
+    return amax
+
+
+def static_scales(amax):
+    """(scale, inv) of a calibrated range: scale = amax / 127 and inv = 127 / amax (0 for a zero
+    range), each ONE IEEE fp32 division, returned as Python floats that hold the fp32 values
+    exactly -- what the kernels receive by value."""
+    import numpy as np
+    a, c127 = np.float32(_check_amax(amax)), np.float32(127.0)
+    if not np.isfinite(a):
+        raise ValueError(f"a quantization range must fit fp32, got {amax}")
+    with np.errstate(over="ignore"):
+        inv = c127 / a if a > 0 else np.float32(0.0)
+    if not np.isfinite(inv):
+        raise ValueError(f"a quantization range this small has no fp32 inverse scale: {amax}")
+    return float(a / c127), float(inv)
+
+
+def quantize_static(x, amax):
+    """Symmetric int8 quantization against a given range instead of the row maximum:
+    q = clamp(rne(x * inv), -127, 127) with one fp32 multiply; values beyond ``amax`` saturate,
+    ``amax == 0`` gives q == 0."""
+    _, inv = static_scales(amax)
+    xf = x.float()
+    return torch.clamp(torch.round(xf * torch.full((), inv, dtype=torch.float32, device=xf.device)),
+                       -127.0, 127.0).to(torch.int8)
+
+
+def linear_i8_static(a_q, a_amax, w_q, w_scale, bias=None, act=ACT_NONE, out_amax=None, dtype=torch.float32):
+    """``linear_i8`` with one activation scale for the whole tensor.  With ``out_amax`` the
+    result, rounded to ``dtype`` first, is quantized against that range and returned as int8."""
+    scale, _ = static_scales(a_amax)
+    a_scale = torch.full((a_q.shape[0],), scale, dtype=torch.float32, device=a_q.device)
+    y = dequant_epilogue(gemm_i8_nt_raw(a_q, w_q), a_scale, w_scale, bias, act, dtype)
+    return y if out_amax is None else quantize_static(y, out_amax)

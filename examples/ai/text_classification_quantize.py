@@ -7,9 +7,16 @@ the int8 one in the same process.
     python examples/ai/text_classification_quantize.py                       # bert-tiny, trains
     python examples/ai/text_classification_quantize.py --model bert-large-uncased --epochs 0 \
         --batch 64 --seq-len 128                                             # latency only
+    python examples/ai/text_classification_quantize.py --approach static     # calibrated ranges
 
-With ``--epochs 0`` the model keeps its random initialisation and quantization runs without an
-accuracy evaluation (there is no accuracy to preserve); the latency comparison is unaffected.
+``--approach static`` calibrates one activation range per site and layer on the evaluation
+dataset (``post_training_static_quant``): the int8 activations then come out of the LayerNorm and
+GEMM epilogues instead of per-token quantize passes.  It also quantizes the same export with the
+dynamic approach and times float, dynamic int8 and static int8 in turn, in this one process.
+
+With ``--epochs 0`` the model keeps its random initialisation and there is no accuracy to
+preserve: the dynamic approach quantizes without an evaluation, the static one still needs the
+dataset to calibrate on and accepts any accuracy; the latency comparison is unaffected.
 Prints one JSON line per benchmark and a final summary line.
 """
 import argparse
@@ -50,6 +57,7 @@ def main():
     ap.add_argument("--seq-len", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--approach", default="dynamic", choices=["dynamic", "static"])
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--device", default=None)
     a = ap.parse_args()
@@ -66,25 +74,39 @@ def main():
 
     saved, out, cfg = os.path.join(work, "fp32"), os.path.join(work, "int8"), os.path.join(work, "quant.yaml")
     m.export(saved)
-    m.export_quantization_config(cfg, ev, batch_size=a.batch, overwrite=True)
-    if m.quantize(saved, out, cfg, dataset=ev if a.epochs > 0 else None) is None:
+    static = a.approach == "static"
+    m.export_quantization_config(cfg, ev, batch_size=a.batch, overwrite=True,
+                                 approach=f"post_training_{a.approach}_quant",
+                                 accuracy_criterion_relative=1.0 if static and a.epochs == 0 else 0.01)
+    if m.quantize(saved, out, cfg, dataset=ev if a.epochs > 0 or static else None) is None:
         print("no trial met the accuracy criterion; nothing written")
         return 1
+    variants = {"fp32": (saved, "fp32"), "int8": (out, "int8")}
+    if static:                                 # the dynamic model of the same export, to time beside it
+        dyn, dyn_cfg = os.path.join(work, "int8_dynamic"), os.path.join(work, "quant_dynamic.yaml")
+        m.export_quantization_config(dyn_cfg, ev, batch_size=a.batch, overwrite=True)
+        if m.quantize(saved, dyn, dyn_cfg, dataset=ev if a.epochs > 0 else None) is not None:
+            variants = {"fp32": (saved, "fp32"), "int8_dynamic": (dyn, "int8"), "int8": (out, "int8")}
     q = load_model(out, device=a.device)
     with open(os.path.join(out, "model_config.json")) as f:
         block = json.load(f)["quantization"]
     probs = q.predict(ev.ids[:4], ev.mask[:4])
-    print(json.dumps({"int8_sites": block["sites"][0], "trial": block["trial"], "accuracy": block["accuracy"],
+    print(json.dumps({"approach": block["approach"], "int8_sites": block["sites"][0], "trial": block["trial"],
+                      "accuracy": block["accuracy"],
                       "predictions": probs.argmax(-1).tolist(), "labels": ev.y[:4].tolist()}), flush=True)
 
     kw = dict(batch_size=a.batch, seq_len=a.seq_len, warmup=a.warmup, iters=a.iters)
     res = {}
-    for rnd in range(2):                       # float, int8, float, int8: the pair repeats on the same box
-        res.setdefault("fp32", []).append(m.benchmark(saved, cfg, model_type="fp32", **kw)["latency_ms"])
-        res.setdefault("int8", []).append(m.benchmark(out, cfg, model_type="int8", **kw)["latency_ms"])
+    for rnd in range(2):                       # float, int8, float, int8: the variants repeat on the same box
+        for name, (path, model_type) in variants.items():
+            res.setdefault(name, []).append(m.benchmark(path, cfg, model_type=model_type, **kw)["latency_ms"])
     fp, i8 = min(res["fp32"]), min(res["int8"])
-    print(json.dumps({"model": a.model, "batch_size": a.batch, "seq_len": a.seq_len, "float_latency_ms": res["fp32"],
-                      "int8_latency_ms": res["int8"], "int8_over_float": round(i8 / fp, 3)}), flush=True)
+    summary = {"model": a.model, "approach": a.approach, "batch_size": a.batch, "seq_len": a.seq_len,
+               "float_latency_ms": res["fp32"], "int8_latency_ms": res["int8"], "int8_over_float": round(i8 / fp, 3)}
+    if "int8_dynamic" in res:
+        summary.update(int8_dynamic_latency_ms=res["int8_dynamic"],
+                       static_over_dynamic=round(i8 / min(res["int8_dynamic"]), 3))
+    print(json.dumps(summary), flush=True)
     if a.epochs > 0:
         m.benchmark(out, cfg, mode="accuracy", model_type="int8", dataset=ev)      # prints its JSON line
     return 0
