@@ -31,6 +31,7 @@ int ct_cast(const void*, int, void*, int, long, float, int, hipStream_t);
 int ct_splitk_reduce(const float*, int, long, void*, int, hipStream_t);
 int ct_splitk_reduce_clear(float*, int, long, void*, int, hipStream_t);
 int ct_splitk_reduce2(const float*, int, long, void*, const float*, int, long, void*, int, hipStream_t);
+int ct_splitk_reduce_group(int, const float* const*, const int*, const long*, void* const*, int, hipStream_t);
 int ct_lamb(const void*, int, float*, float*, float*, void*, int, const int*, const long*,
             const int*, int, const int*, int, const float*, const float*, float, float, float, int,
             int, float*, float*, int, hipStream_t);
@@ -292,6 +293,27 @@ void splitk_reduce2(at::Tensor p1, at::Tensor g1, at::Tensor p2, at::Tensor g2, 
   TORCH_CHECK(ct_splitk_reduce2(p1.data_ptr<float>(), (int)p1.size(0), g1.numel(), g1.data_ptr(),
                                 p2.data_ptr<float>(), (int)p2.size(0), g2.numel(), g2.data_ptr(),
                                 accumulate ? 1 : 0, cur_stream()) == 0);
+}
+
+// up to 4 (partials, g) reductions in one launch (see ct_splitk_reduce_group)
+void splitk_reduce_group(std::vector<at::Tensor> partials, std::vector<at::Tensor> gs, bool accumulate) {
+  const size_t n = partials.size();
+  TORCH_CHECK(n >= 1 && n <= 4 && gs.size() == n, "splitk_reduce_group: 1..4 (partials, g) pairs");
+  std::vector<const float*> P(n);
+  std::vector<void*> g(n);
+  std::vector<int> S(n);
+  std::vector<long> len(n);
+  for (size_t i = 0; i < n; ++i) {
+    CHECK_IN(partials[i]); CHECK_F32(partials[i]); CHECK_IN(gs[i]); CHECK_BF16(gs[i]);
+    TORCH_CHECK(partials[i].dim() >= 2 && partials[i][0].numel() == gs[i].numel(), "splitk_reduce_group: shape mismatch");
+    TORCH_CHECK(gs[i].numel() > 0 && gs[i].numel() % 8 == 0, "splitk_reduce_group: numel % 8");
+    P[i] = partials[i].data_ptr<float>();
+    g[i] = gs[i].data_ptr();
+    S[i] = (int)partials[i].size(0);
+    len[i] = gs[i].numel();
+  }
+  TORCH_CHECK(ct_splitk_reduce_group((int)n, P.data(), S.data(), len.data(), g.data(), accumulate ? 1 : 0,
+                                     cur_stream()) == 0, "splitk_reduce_group: misaligned tensor");
 }
 
 void splitk_reduce_clear(at::Tensor partials, at::Tensor g, bool accumulate) {
@@ -857,6 +879,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("splitk_reduce", &splitk_reduce);
   m.def("splitk_reduce_clear", &splitk_reduce_clear);
   m.def("splitk_reduce2", &splitk_reduce2);
+  m.def("splitk_reduce_group", &splitk_reduce_group);
   m.def("lamb_step", &lamb_step);
   m.def("adam_step", &adam_step);
   m.def("sgd_step", &sgd_step);

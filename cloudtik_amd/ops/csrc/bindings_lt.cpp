@@ -439,7 +439,52 @@ bool gemm_tn2_bias(at::Tensor A, at::Tensor B, at::Tensor out, int64_t splits, b
   return gemm_tn2_impl(A, B, out, splits, accumulate, biasg.data_ptr<float>());
 }
 
+extern "C" int ct_gemm_tn_group(int, const void* const*, const long*, const void* const*, const long*, float* const*,
+                                float* const*, const int*, const int*, long, int, hipStream_t);
+
+// Several weight-gradient GEMMs that share the token count K and one slice count in one launch:
+// P[i] (fp32 [splits, M_i, N_i]) = per-slice A[i][K, M_i]^T @ B[i][K, N_i]; biasg[i] (None or fp32
+// [splits, M_i]) = per-slice column sums of A[i].  False (nothing launched) when the native
+// entry refuses (more than 4 problems, splits < 2, a shape outside the tiling, misalignment).
+bool gemm_tn_group(std::vector<at::Tensor> A, std::vector<at::Tensor> B, std::vector<at::Tensor> P,
+                   std::vector<c10::optional<at::Tensor>> biasg, int64_t splits) {
+  const size_t n = A.size();
+  TORCH_CHECK(n >= 1 && B.size() == n && P.size() == n && biasg.size() == n, "gemm_tn_group: list lengths");
+  std::vector<const void*> a(n), b(n);
+  std::vector<float*> p(n), bg(n);
+  std::vector<long> lda(n), ldb(n);
+  std::vector<int> Ms(n), Ns(n);
+  const long K = A[0].dim() == 2 ? A[0].size(0) : -1;
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(A[i].is_cuda() && B[i].is_cuda() && P[i].is_cuda(), "gemm_tn_group: GPU tensors");
+    TORCH_CHECK(A[i].scalar_type() == at::kBFloat16 && B[i].scalar_type() == at::kBFloat16,
+                "gemm_tn_group: bf16 operands");
+    TORCH_CHECK(rowmajor_ok(A[i]) && rowmajor_ok(B[i]), "gemm_tn_group: 2-D row-major operands");
+    TORCH_CHECK(A[i].size(0) == K && B[i].size(0) == K, "gemm_tn_group: K mismatch");
+    const long M = A[i].size(1), N = B[i].size(1);
+    TORCH_CHECK(M < (1L << 31) && N < (1L << 31), "gemm_tn_group: dimension too large");
+    TORCH_CHECK(P[i].scalar_type() == at::kFloat && P[i].is_contiguous() && P[i].dim() == 3 && P[i].size(0) == splits &&
+                P[i].size(1) == M && P[i].size(2) == N, "gemm_tn_group: fp32 [splits, M, N] slabs");
+    const bool hb = biasg[i].has_value() && biasg[i]->defined();
+    if (hb)
+      TORCH_CHECK(biasg[i]->is_cuda() && biasg[i]->scalar_type() == at::kFloat && biasg[i]->is_contiguous() &&
+                  biasg[i]->numel() == splits * M, "gemm_tn_group: fp32 [splits, M] bias partials");
+    a[i] = A[i].data_ptr();
+    b[i] = B[i].data_ptr();
+    p[i] = P[i].data_ptr<float>();
+    bg[i] = hb ? biasg[i]->data_ptr<float>() : nullptr;
+    lda[i] = A[i].stride(0);
+    ldb[i] = B[i].stride(0);
+    Ms[i] = (int)M;
+    Ns[i] = (int)N;
+  }
+  return ct_gemm_tn_group((int)n, a.data(), lda.data(), b.data(), ldb.data(), p.data(), bg.data(), Ms.data(),
+                          Ns.data(), K, (int)std::min<int64_t>(splits, 1 << 30),
+                          at::hip::getCurrentHIPStream().stream()) == 0;
+}
+
 void register_lt(pybind11::module& m) {
+  m.def("gemm_tn_group", &gemm_tn_group, "several gemm_tn2 problems sharing K and the slice count, one launch");
   m.def("gemm_tn2", &gemm_tn2, "weight-gradient GEMM A^T @ B (token-major operands) on the MFMA kernel");
   m.def("gemm_tn2_bias", &gemm_tn2_bias, "gemm_tn2 + per-split column sums of A (bias gradient)");
   m.def("gemm_nt", &gemm_nt, "hand-written MFMA GEMM A @ B^T with fused epilogues");

@@ -411,6 +411,74 @@ extern "C" int ct_splitk_reduce2(const float* P, int S, long n, void* g, const f
   return 0;
 }
 
+// The same for up to 4 (P, S, n, g) entries in one launch: the slabs of the two weight
+// gradients of a grouped split-K GEMM (ct_gemm_tn_group) and a bias's column-sum partials.
+// Slices are summed in ascending order (fp32), 8 elements per thread, optional g +=.
+constexpr int REDUCE_GROUP_MAX = 4;
+struct ReduceGroup {
+  const float* P[REDUCE_GROUP_MAX];
+  bf16_t* g[REDUCE_GROUP_MAX];
+  long nv[REDUCE_GROUP_MAX];
+  long first[REDUCE_GROUP_MAX];   // first vector of entry k in the launch (LONG_MAX: unused)
+  int S[REDUCE_GROUP_MAX];
+  long total;
+};
+
+__global__ void __launch_bounds__(256) splitk_reduce_group_kernel(ReduceGroup r, int accumulate) {
+  for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < r.total; t += (long)gridDim.x * blockDim.x) {
+    const float* P = r.P[0];
+    bf16_t* g = r.g[0];
+    long n = r.nv[0] * 8, v = t;
+    int S = r.S[0];
+#pragma unroll
+    for (int k = 1; k < REDUCE_GROUP_MAX; ++k)
+      if (t >= r.first[k]) {
+        P = r.P[k]; g = r.g[k]; n = r.nv[k] * 8; v = t - r.first[k]; S = r.S[k];
+      }
+    float acc[8];
+    if (accumulate) {
+      const u16x8 gv = *reinterpret_cast<const u16x8*>(g + v * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = bf2f(gv[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    }
+#pragma unroll 4
+    for (int s = 0; s < S; ++s) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(P + s * n + v * 8);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(P + s * n + v * 8 + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { acc[j] += a[j]; acc[4 + j] += b[j]; }
+    }
+    u16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = f2bf(acc[j]);
+    *reinterpret_cast<u16x8*>(g + v * 8) = o;
+  }
+}
+
+extern "C" int ct_splitk_reduce_group(int count, const float* const* P, const int* S, const long* n, void* const* g,
+                                      int accumulate, hipStream_t stream) {
+  if (count < 1 || count > REDUCE_GROUP_MAX) return -1;
+  ReduceGroup r{};
+  long total = 0;
+  for (int k = 0; k < REDUCE_GROUP_MAX; ++k) r.first[k] = 0x7fffffffffffffffL;
+  for (int k = 0; k < count; ++k) {
+    if (n[k] <= 0 || n[k] % 8 || S[k] < 1 || !P[k] || !g[k] || ((uintptr_t)P[k] & 15) || ((uintptr_t)g[k] & 15))
+      return -1;
+    r.P[k] = P[k];
+    r.g[k] = (bf16_t*)g[k];
+    r.nv[k] = n[k] / 8;
+    r.first[k] = total;
+    r.S[k] = S[k];
+    total += r.nv[k];
+  }
+  r.total = total;
+  splitk_reduce_group_kernel<<<grid_for(total), 256, 0, stream>>>(r, accumulate);
+  return 0;
+}
+
 extern "C" int ct_splitk_reduce_clear(float* P, int S, long n, void* g, int accumulate, hipStream_t stream) {
   if (n % 8) return -1;
   const long nv = n / 8;

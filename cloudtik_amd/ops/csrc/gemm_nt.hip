@@ -704,6 +704,114 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Grouped weight-gradient GEMM (TN layout, split-K fp32 slabs): up to NT_GROUP_MAX problems
+// D_i[M_i, N_i] = A_i[K, M_i]^T B_i[K, N_i] that share K (the token count) and one slice count
+// in ONE grid of splits * (sum of the problems' tiles) workgroups.  The slices of a lone
+// weight gradient exist only to fill the CUs (48 or 16 tiles on 256 CUs); two gradients of one
+// transformer block fill them together with half the slices, so half the fp32 slab bytes are
+// written and read back, and one launch replaces two.  A workgroup finds its slice, then its
+// tile in the union of the problems' tiles, then the problem (tile-base table); everything
+// after that is gemm_nt_kernel<NT_EPI_F32_SLAB, false, 0, 1, true> on that problem's
+// operands: same staging, phases, fragment reads and K-tile deal.  The bias column sums are a
+// per-problem runtime choice (biasg_i != null).  A separate __global__ so the register
+// allocation of the single-problem instantiations cannot change.
+constexpr int NT_GROUP_MAX = 4;
+
+struct NtGroupArgs {
+  const bf16_t* A[NT_GROUP_MAX];
+  const bf16_t* B[NT_GROUP_MAX];
+  float* P[NT_GROUP_MAX];          // fp32 slabs [splits][M_i][N_i]
+  float* biasg[NT_GROUP_MAX];      // fp32 [splits][M_i] column sums of A_i, or null
+  long lda[NT_GROUP_MAX], ldb[NT_GROUP_MAX];
+  int M[NT_GROUP_MAX], N[NT_GROUP_MAX];
+  int tile_base[NT_GROUP_MAX];     // first union tile of problem i (INT_MAX for unused entries)
+  int tiles_total;
+  int K, tsplit;
+};
+
+// It is an overload of gemm_nt_kernel on the argument type, instantiated only as
+// <NT_EPI_F32_SLAB, false, 0, 1, true>: profiles and tools that look for the TN weight-gradient
+// kernel by its template arguments find both forms, told apart by (NtArgs) / (NtGroupArgs).
+template <int EPI, bool BGRAD, int DIAG, int LAY, bool BIASG>
+__global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtGroupArgs g) {
+  static_assert(EPI == NT_EPI_F32_SLAB && !BGRAD && DIAG == 0 && LAY == 1 && BIASG,
+                "the grouped form exists for TN split-K slabs with runtime bias sums only");
+  __shared__ __attribute__((aligned(1024))) char lds[2 * NT_BUF];    // 128 KiB, the only LDS object
+  int L = xcd_remap(blockIdx.x, gridDim.x);
+  const int split = L / g.tiles_total;
+  L -= split * g.tiles_total;
+  // the problem this union tile belongs to (compile-time indices: the table stays in SGPRs)
+  NtArgs a{};
+  a.A = g.A[0]; a.B = g.B[0]; a.P = g.P[0]; a.biasg = g.biasg[0];
+  a.lda = g.lda[0]; a.ldb = g.ldb[0]; a.M = g.M[0]; a.N = g.N[0];
+  int base = 0;
+#pragma unroll
+  for (int i = 1; i < NT_GROUP_MAX; ++i)
+    if (L >= g.tile_base[i]) {
+      a.A = g.A[i]; a.B = g.B[i]; a.P = g.P[i]; a.biasg = g.biasg[i];
+      a.lda = g.lda[i]; a.ldb = g.ldb[i]; a.M = g.M[i]; a.N = g.N[i];
+      base = g.tile_base[i];
+    }
+  L -= base;
+  a.K = g.K;
+  a.tsplit = g.tsplit;
+  const int tiles_n = a.N / NT_BN;
+  const int tm = L / tiles_n, tn = L % tiles_n;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 2, wc = wave & 3;
+  const long m0 = (long)tm * NT_BM, n0 = (long)tn * NT_BN;
+  const int kt_all = a.K / NT_BK;
+  const int kt_q = kt_all / (int)a.tsplit, kt_r = kt_all % (int)a.tsplit;
+  const int nk = kt_q + (split < kt_r ? 1 : 0);
+  const long kfirst = (long)(split * kt_q + min(split, kt_r)) * NT_BK;
+  NtCtx c{a.A, a.B, a.lda, a.ldb, m0, n0, kfirst, lds, wave, lane, wr * 64, wc * 32,
+          0, 0, 0, 0, (a.biasg != nullptr && tn == 0) ? 2 * wc : -1, 0};
+  f32x4 accb[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  c.offa0 = c.offa1 = tn_lane_off(a.lda, wave, lane, true);
+  c.offb0 = c.offb1 = tn_lane_off(a.ldb, wave, lane, false);
+
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const long emrow = m0 + wr * 128 + (lane & 15), encol = n0 + wc * 64 + (lane >> 4) * 4;
+  NtEpiPre<4> epre;
+
+  nt_s16x8 fa[2][4][2];
+  nt_s16x8 fb[2][2][2];
+
+#pragma unroll
+  for (int v = -6; v < -2; ++v) nt_stage_v<LAY>(c, v);
+  if (nk > 1) {
+    nt_stage_v<LAY>(c, -2);
+    nt_stage_v<LAY>(c, -1);
+    nt_vm<8>();
+  } else {
+    nt_vm<4>();
+  }
+  nt_bar();
+  if (wr == 1) nt_bar();                                 // group 1 runs one barrier behind
+
+  int t = 0;
+  for (; t < nk - 2; ++t) nt_ktile<0, 0, LAY, true>(c, t, acc, fa, fb, accb);
+  if (nk >= 2) {
+    nt_ktile<1, 0, LAY, true>(c, t, acc, fa, fb, accb);
+    ++t;
+  }
+  nt_ktile<2, 0, LAY, true>(c, t, acc, fa, fb, accb);
+  if (wr == 0) nt_bar();                                 // equal barrier counts for both groups
+
+  nt_epilogue<NT_EPI_F32_SLAB, false, 4>(a, acc, emrow, encol, lane, split, epre, 0);
+  if (c.biasw >= 0 && lane < 16) {
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2)
+      a.biasg[(long)split * a.M + m0 + wr * 128 + 16 * (c.biasw + t2) + lane] = accb[t2][0];
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // Streamed persistent variant (forward / data-gradient GEMMs, NT and NN layouts).
 //
 // One workgroup per CU walks several output tiles (w, w + P, w + 2P, ... in the XCD-remapped
@@ -1244,6 +1352,43 @@ extern "C" int ct_gemm_tn2(const void* A, long lda, const void* B, long ldb, voi
     if (splits > 1) gemm_nt_kernel<NT_EPI_F32_SLAB, false, 0, 1><<<(int)blocks, NT_THREADS, 0, stream>>>(a);
     else gemm_nt_kernel<NT_EPI_PLAIN, false, 0, 1><<<(int)blocks, NT_THREADS, 0, stream>>>(a);
   }
+  return hipGetLastError() == hipSuccess ? 0 : 7;
+}
+
+// Grouped weight-gradient GEMM: nprob (1..4) problems P_i[splits][M_i][N_i] = per-slice
+// A_i[K, M_i]^T . B_i[K, N_i] in one launch of splits * sum(tiles_i) workgroups (gemm_nt_kernel(NtGroupArgs));
+// all share K and splits >= 2.  biasg[i] (may be null): fp32 [splits][M_i] column sums of A_i.
+// Operand rules as ct_gemm_tn2.  Nonzero (nothing launched) when unsupported.
+extern "C" int ct_gemm_tn_group(int nprob, const void* const* A, const long* lda, const void* const* B,
+                                const long* ldb, float* const* P, float* const* biasg, const int* M, const int* N,
+                                long K, int splits, hipStream_t stream) {
+  if (nprob < 1 || nprob > NT_GROUP_MAX || splits < 2) return 1;
+  if (K <= 0 || K % NT_BK || K / NT_BK < splits || K > (1L << 30)) return 2;
+  NtGroupArgs g{};
+  long tiles = 0;
+  for (int i = 0; i < NT_GROUP_MAX; ++i) g.tile_base[i] = 0x7fffffff;
+  for (int i = 0; i < nprob; ++i) {
+    if (M[i] <= 0 || N[i] <= 0 || M[i] % NT_BM || N[i] % NT_BN) return 1;
+    if (lda[i] % 8 || ldb[i] % 8 || lda[i] < M[i] || ldb[i] < N[i] || !A[i] || !B[i] || ((uintptr_t)A[i] & 15) ||
+        ((uintptr_t)B[i] & 15))
+      return 3;
+    if (!P[i] || ((uintptr_t)P[i] & 15) || (biasg[i] && ((uintptr_t)biasg[i] & 3))) return 4;
+    g.A[i] = (const bf16_t*)A[i];
+    g.B[i] = (const bf16_t*)B[i];
+    g.P[i] = P[i];
+    g.biasg[i] = biasg[i];
+    g.lda[i] = lda[i];
+    g.ldb[i] = ldb[i];
+    g.M[i] = M[i];
+    g.N[i] = N[i];
+    g.tile_base[i] = (int)tiles;
+    tiles += (long)(M[i] / NT_BM) * (N[i] / NT_BN);
+    if (tiles * splits > (1L << 30)) return 5;
+  }
+  g.tiles_total = (int)tiles;
+  g.K = (int)K;
+  g.tsplit = splits;
+  gemm_nt_kernel<NT_EPI_F32_SLAB, false, 0, 1, true><<<(int)(tiles * splits), NT_THREADS, 0, stream>>>(g);
   return hipGetLastError() == hipSuccess ? 0 : 7;
 }
 

@@ -42,7 +42,26 @@ _HIP_WGRAD = os.environ.get("CLOUDTIK_AMD_WGRAD_KERNEL", "hip") == "hip"
 # chosen by timing every solution once per shape (torch.bmm's heuristic pick is not tuned:
 # TunableOp skips bf16 -> fp32 batched GEMMs)
 _LT_WGRAD = os.environ.get("CLOUDTIK_AMD_WGRAD_LT", "0") == "1"
+# The two weight gradients of one transformer block (Wo + Wqkv, W2 + W1) as ONE grouped split-K
+# launch (csrc/gemm_nt.hip ct_gemm_tn_group) + ONE grouped reduce: together they fill the CUs
+# with half the slices, so half the fp32 slab bytes are written and read back, and four launches
+# per block become two.  BERT-large, one MI355X, interleaved rounds on one box
+# (profiles/wgrad_group/SUMMARY.md): in line 70.85-70.93 -> 69.96-70.10 ms/step, on the side
+# stream 70.19-70.39 -> 69.66-69.92, so it is on for both routings.  CLOUDTIK_AMD_WGRAD_GROUP
+# (0 / 1) pins it; with 0 the issue order and the kernels are those of the ungrouped path.
+_WGRAD_GROUP_ENV = os.environ.get("CLOUDTIK_AMD_WGRAD_GROUP")
+_WGRAD_GROUP_INLINE_DEFAULT = True
+_WGRAD_GROUP_SIDE_DEFAULT = True
 _streams = {}
+
+
+def wgrad_group_enabled(side: bool, pair: str = "") -> bool:
+    """Whether a block's weight gradients are issued as one grouped launch; ``side``: the
+    weights' routing (side stream or in line); ``pair``: "attn" (Wo + Wqkv) or "ffn" (W2 + W1)
+    -- CLOUDTIK_AMD_WGRAD_GROUP=attn / ffn groups that pair alone (for measuring them apart)."""
+    if _WGRAD_GROUP_ENV is not None:
+        return _WGRAD_GROUP_ENV == "1" or (pair != "" and _WGRAD_GROUP_ENV == pair)
+    return _WGRAD_GROUP_SIDE_DEFAULT if side else _WGRAD_GROUP_INLINE_DEFAULT
 
 
 def grad_stream():
@@ -131,6 +150,23 @@ def wgrad_on_side_stream(g: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor,
     return True
 
 
+def wgrad_group_on_side_stream(items, enabled: bool = True) -> bool:
+    """``wgrad_accumulate_group(items)`` on the gradient side stream (the grouped form of
+    ``wgrad_on_side_stream``: the same ordering and lifetime handling for every operand);
+    False (nothing issued) when ``enabled`` is False or there is no GPU."""
+    s = side_grad_stream() if (enabled and all(it[0].is_cuda for it in items)) else None
+    if s is None:
+        return False
+    cur = torch.cuda.current_stream()
+    s.wait_stream(cur)
+    with torch.cuda.stream(s):
+        wgrad_accumulate_group(items)
+    for _g, dy2, x2, _db in items:
+        dy2.record_stream(s)
+        x2.record_stream(s)
+    return True
+
+
 def splitk_factor(T: int, N: int, K: int) -> int:
     """Split factor for dW[N,K] = dY[T,N]^T X[T,K].  hipBLASLt's 256x256 macro-tiles give only
     ceil(N/256)*ceil(K/256) workgroups (16..192 for BERT-large), far fewer than the 256 CUs;
@@ -166,6 +202,91 @@ def tn2_splits(T: int, N: int, K: int, cus: int = 256) -> int:
         if best_cost is None or cost < best_cost * (1 - 1e-9):
             best, best_cost = S, cost
     return best
+
+
+def tn2_group_splits(T: int, shapes, cus: int = 256) -> int:
+    """Slice count shared by several weight gradients dW_i[N_i, K_i] issued as one grouped
+    launch: the ``tn2_splits`` cost model over the summed tile count and the summed FLOPs.
+    BERT-large (T = 32768): Wo + Wqkv 64 tiles -> 4, W2 + W1 128 tiles -> 2.  1 when a shape is
+    outside the kernel's tiling."""
+    shapes = list(shapes)
+    if not shapes or T % 64 or any(N <= 0 or K <= 0 or N % 256 or K % 256 for N, K in shapes):
+        return 1
+    tiles = sum((N // 256) * (K // 256) for N, K in shapes)
+    t_full = 2.0 * sum(N * K for N, K in shapes) * T / 1.3e15
+    best, best_cost = 1, None
+    for S in range(1, 33):
+        if S > 1 and (T // S < 512 or T // 64 < S):
+            continue
+        waves = -(-tiles * S // cus)
+        cost = t_full * waves * cus / (tiles * S) + (S * tiles * 262144 * 2 / 5e12 if S > 1 else 0.0)
+        if best_cost is None or cost < best_cost * (1 - 1e-9):
+            best, best_cost = S, cost
+    return best
+
+
+_GROUP_MAX = 4      # problems per grouped GEMM launch, entries per grouped reduce launch
+
+
+def _group_qualifies(items) -> bool:
+    """The conditions of ``wgrad_accumulate``'s MFMA path for every problem, one token count
+    and one device for all, and gradients the grouped reduce can write (contiguous, 16-byte
+    aligned)."""
+    if not (_HIP_WGRAD and 2 <= len(items) <= _GROUP_MAX):
+        return False
+    T, dev = items[0][1].shape[0], items[0][0].device
+    for g, dy2, x2, _db in items:
+        if dy2.dim() != 2 or x2.dim() != 2 or dy2.shape[0] != T or x2.shape[0] != T:
+            return False
+        N, K = dy2.shape[1], x2.shape[1]
+        if not (g.is_cuda and g.device == dev and g.dtype == torch.bfloat16 and dy2.dtype == torch.bfloat16
+                and x2.dtype == torch.bfloat16 and N % 256 == 0 and K % 256 == 0 and T % 64 == 0):
+            return False
+        if tuple(g.shape) != (N, K) or not g.is_contiguous() or g.data_ptr() % 16:
+            return False
+    return True
+
+
+def wgrad_accumulate_group(items) -> None:
+    """``wgrad_accumulate(g, dy2, x2, dbias)`` for every ``(g, dy2, x2, dbias)`` of ``items``
+    (weight gradients over the same tokens, e.g. the two of one transformer block) as one
+    grouped split-K GEMM into one fp32 workspace and one grouped reduce.  Falls back to the
+    per-problem calls when the slice chooser returns 1, a tensor does not qualify or the
+    native entry refuses."""
+    items = list(items)
+    S = 1
+    if _group_qualifies(items):
+        S = tn2_group_splits(items[0][1].shape[0], [(dy2.shape[1], x2.shape[1]) for _g, dy2, x2, _db in items])
+    if S < 2:
+        for it in items:
+            wgrad_accumulate(*it)
+        return
+    from cloudtik_amd import ops
+    C = ops.require_native()
+    fuse = [(_WGRAD_BIAS_FUSE and db is not None and db.dtype == torch.bfloat16 and db.is_contiguous()
+             and db.data_ptr() % 16 == 0) for _g, _dy2, _x2, db in items]
+    sizes = [S * dy2.shape[1] * x2.shape[1] for _g, dy2, x2, _db in items]
+    bsizes = [S * it[1].shape[1] if f else 0 for it, f in zip(items, fuse)]
+    ws = torch.empty(sum(sizes) + sum(bsizes), device=items[0][0].device, dtype=torch.float32)
+    A, B, P, bP, off = [], [], [], [], 0
+    for (_g, dy2, x2, _db), n in zip(items, sizes):
+        A.append(dy2.contiguous())
+        B.append(x2.contiguous())
+        P.append(ws[off:off + n].view(S, dy2.shape[1], x2.shape[1]))
+        off += n
+    for (_g, dy2, _x2, _db), n in zip(items, bsizes):
+        bP.append(ws[off:off + n].view(S, dy2.shape[1]) if n else None)
+        off += n
+    if not C.gemm_tn_group(A, B, P, bP, S):
+        for it in items:
+            wgrad_accumulate(*it)
+        return
+    red = [(p, it[0]) for p, it in zip(P, items)] + [(b, it[3]) for b, it in zip(bP, items) if b is not None]
+    for i in range(0, len(red), _GROUP_MAX):
+        C.splitk_reduce_group([p for p, _ in red[i:i + _GROUP_MAX]], [g for _, g in red[i:i + _GROUP_MAX]], True)
+    for (_g, dy2, _x2, db), f in zip(items, fuse):
+        if db is not None and not f:
+            _bias_colsum(db, dy2)
 
 
 def _bias_colsum(dbias: torch.Tensor, dy2: torch.Tensor) -> None:

@@ -25,7 +25,8 @@ import os
 
 import torch
 
-from cloudtik_amd.ops.linear import wgrad_accumulate, wgrad_on_side_stream, wgrad_side
+from cloudtik_amd.ops.linear import (wgrad_accumulate, wgrad_accumulate_group, wgrad_group_enabled,
+                                     wgrad_group_on_side_stream, wgrad_on_side_stream, wgrad_side)
 
 
 def _C():
@@ -214,6 +215,25 @@ def _wgrad(p, dy2, x2, bias=None):
     return dy2.t() @ x2
 
 
+def _group_ok(pa, pb, pair) -> bool:
+    """Whether the weight gradients of ``pa`` and ``pb`` (one block, same tokens) go out as one
+    grouped launch: both flat, same routing, grouping enabled for that routing and ``pair``."""
+    return (_flat(pa) and _flat(pb) and wgrad_side(pa) == wgrad_side(pb)
+            and wgrad_group_enabled(wgrad_side(pa), pair))
+
+
+def _wgrad_group(items):
+    """``_wgrad(p, dy2, x2, bias)`` for every ``(p, dy2, x2, bias)`` of ``items`` (all flat, one
+    routing: ``_group_ok``) as one grouped split-K GEMM + one grouped reduce."""
+    args = [(p.grad, dy2, x2, b.grad if b is not None else None) for p, dy2, x2, b in items]
+    if not wgrad_group_on_side_stream(args, enabled=wgrad_side(items[0][0])):
+        wgrad_accumulate_group(args)
+    for p, _dy2, _x2, b in items:
+        _ready(p)
+        if b is not None:
+            _ready(b)
+
+
 def _vec_grad_out(p):
     """(target tensor for an accumulating kernel, whether it is the flat grad)."""
     if _flat(p):
@@ -272,7 +292,9 @@ class _AttnBlockFn(torch.autograd.Function):
             da = ds
         _ready(*[p for p, f in ((g1, fg1), (b1, fb1), (bo, fbo)) if f])
         o2 = o.view(B * S, H)
-        dWo = _wgrad(Wo, da, o2)
+        # grouped: the Wo gradient waits for dqkv and goes out with the Wqkv one (one launch)
+        hold_wo = _group_ok(Wo, Wqkv, "attn")
+        dWo = None if hold_wo else _wgrad(Wo, da, o2)
         do = _stream_mm("do", da, Wo, True, side=wgrad_side(Wo))
         if do is None:
             do = torch.mm(da, Wo)
@@ -284,12 +306,18 @@ class _AttnBlockFn(torch.autograd.Function):
                    kb if has_kb else None, lse, scale, p_attn, seed_a, off_a, False)
         dbq, fbq = _vec_grad_out(bqkv)
         if fbq and _flat(Wqkv):
-            dWqkv = _wgrad(Wqkv, dqkv, x2, bias=bqkv)          # bias grad fused into the wgrad GEMM
+            if hold_wo:
+                dWqkv = _wgrad_group([(Wo, da, o2, None), (Wqkv, dqkv, x2, bqkv)])
+            else:
+                dWqkv = _wgrad(Wqkv, dqkv, x2, bias=bqkv)      # bias grad fused into the wgrad GEMM
         else:
             C.bias_act_bwd_into(dqkv, dqkv, None, 0, dbq, False)   # column sum of dqkv
             if fbq:
                 _ready(bqkv)
-            dWqkv = _wgrad(Wqkv, dqkv, x2)
+            if hold_wo:
+                dWqkv = _wgrad_group([(Wo, da, o2, None), (Wqkv, dqkv, x2, None)])
+            else:
+                dWqkv = _wgrad(Wqkv, dqkv, x2)
         dx = _stream_mm("dx_attn", dqkv, Wqkv, True, out=ds, side=wgrad_side(Wqkv))
         if dx is None:
             dx = ds.addmm_(dqkv, Wqkv)    # residual grad fused: in-place beta=1 epilogue, no C copy
@@ -342,13 +370,18 @@ class _FFNBlockFn(torch.autograd.Function):
         if not need_dx:
             df = ds
         _ready(*[p for p, f in ((g2, fg2), (b2, fb2), (b2f, fb2f)) if f])
-        dW2 = _wgrad(W2, df, h)
+        # grouped: the W2 gradient waits for dz and goes out with the W1 one (one launch)
+        hold_w2 = _group_ok(W2, W1, "ffn")
+        dW2 = None if hold_w2 else _wgrad(W2, df, h)
         db1f, fb1f = _vec_grad_out(b1f)
         bias_in_wgrad = _FFN_BGRAD_IN_WGRAD and dgelu and fb1f and _flat(W1)
         dz = (_fused_ffn_dgrad(C, df.contiguous(), W2, z, zbias, None if bias_in_wgrad else db1f, dgelu)
               if _FUSED_FFN_DGRAD else None)
         if dz is not None and bias_in_wgrad:
-            dW1 = _wgrad(W1, dz, x2, bias=b1f)         # bias gradient fused into the wgrad GEMM
+            if hold_w2:
+                dW1 = _wgrad_group([(W2, df, h, None), (W1, dz, x2, b1f)])
+            else:
+                dW1 = _wgrad(W1, dz, x2, bias=b1f)     # bias gradient fused into the wgrad GEMM
             dx = _stream_mm("dx_ffn", dz, W1, True, out=ds, side=wgrad_side(W1))
             if dx is None:
                 dx = ds.addmm_(dz, W1)
@@ -363,7 +396,10 @@ class _FFNBlockFn(torch.autograd.Function):
             dz = C.bias_act_bwd_into(dh, z, zbias, 1, db1f, True)
         if fb1f:
             _ready(b1f)
-        dW1 = _wgrad(W1, dz, x2)
+        if hold_w2:
+            dW1 = _wgrad_group([(W2, df, h, None), (W1, dz, x2, None)])
+        else:
+            dW1 = _wgrad(W1, dz, x2)
         dx = _stream_mm("dx_ffn", dz, W1, True, out=ds, side=wgrad_side(W1))
         if dx is None:
             dx = ds.addmm_(dz, W1)
