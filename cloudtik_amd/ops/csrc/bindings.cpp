@@ -276,20 +276,23 @@ void cast_into(at::Tensor x, at::Tensor y, double scale, bool accumulate) {
   ct_cast(x.data_ptr(), dt_code(x), y.data_ptr(), dt_code(y), x.numel(), (float)scale, accumulate ? 1 : 0, cur_stream());
 }
 
+// one (partials [S, ...] fp32, g bf16) pair of a split-K reduce entry
+static void check_reduce_pair(const char* who, const at::Tensor& partials, const at::Tensor& g) {
+  CHECK_IN(partials); CHECK_F32(partials); CHECK_IN(g); CHECK_BF16(g);
+  TORCH_CHECK(partials.dim() >= 2 && partials[0].numel() == g.numel(), who, ": shape mismatch");
+  TORCH_CHECK(g.numel() % 8 == 0, who, ": numel must be a multiple of 8");
+}
+
 void splitk_reduce(at::Tensor partials, at::Tensor g, bool accumulate) {
-  CHECK_IN(partials); CHECK_IN(g); CHECK_F32(partials); CHECK_BF16(g);
-  TORCH_CHECK(partials.dim() >= 2 && partials[0].numel() == g.numel(), "splitk_reduce: shape mismatch");
-  TORCH_CHECK(g.numel() % 8 == 0, "splitk_reduce: numel must be a multiple of 8");
+  check_reduce_pair("splitk_reduce", partials, g);
   TORCH_CHECK(ct_splitk_reduce(partials.data_ptr<float>(), (int)partials.size(0), g.numel(), g.data_ptr(),
                                accumulate ? 1 : 0, cur_stream()) == 0);
 }
 
-// the same, and the partials are zeroed once read (persistent accumulation buffers)
 // two (partials, g) reductions in one launch (see ct_splitk_reduce2)
 void splitk_reduce2(at::Tensor p1, at::Tensor g1, at::Tensor p2, at::Tensor g2, bool accumulate) {
-  for (auto* t : {&p1, &p2}) { CHECK_IN(*t); TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() >= 2); }
-  for (auto* t : {&g1, &g2}) { CHECK_IN(*t); CHECK_BF16(*t); TORCH_CHECK(t->numel() % 8 == 0, "splitk_reduce2: numel % 8"); }
-  TORCH_CHECK(p1[0].numel() == g1.numel() && p2[0].numel() == g2.numel(), "splitk_reduce2: shape mismatch");
+  check_reduce_pair("splitk_reduce2", p1, g1);
+  check_reduce_pair("splitk_reduce2", p2, g2);
   TORCH_CHECK(ct_splitk_reduce2(p1.data_ptr<float>(), (int)p1.size(0), g1.numel(), g1.data_ptr(),
                                 p2.data_ptr<float>(), (int)p2.size(0), g2.numel(), g2.data_ptr(),
                                 accumulate ? 1 : 0, cur_stream()) == 0);
@@ -304,9 +307,8 @@ void splitk_reduce_group(std::vector<at::Tensor> partials, std::vector<at::Tenso
   std::vector<int> S(n);
   std::vector<long> len(n);
   for (size_t i = 0; i < n; ++i) {
-    CHECK_IN(partials[i]); CHECK_F32(partials[i]); CHECK_IN(gs[i]); CHECK_BF16(gs[i]);
-    TORCH_CHECK(partials[i].dim() >= 2 && partials[i][0].numel() == gs[i].numel(), "splitk_reduce_group: shape mismatch");
-    TORCH_CHECK(gs[i].numel() > 0 && gs[i].numel() % 8 == 0, "splitk_reduce_group: numel % 8");
+    check_reduce_pair("splitk_reduce_group", partials[i], gs[i]);
+    TORCH_CHECK(gs[i].numel() > 0, "splitk_reduce_group: empty tensor");
     P[i] = partials[i].data_ptr<float>();
     g[i] = gs[i].data_ptr();
     S[i] = (int)partials[i].size(0);
@@ -316,10 +318,9 @@ void splitk_reduce_group(std::vector<at::Tensor> partials, std::vector<at::Tenso
                                      cur_stream()) == 0, "splitk_reduce_group: misaligned tensor");
 }
 
+// splitk_reduce, and the partials are zeroed once read (persistent accumulation buffers)
 void splitk_reduce_clear(at::Tensor partials, at::Tensor g, bool accumulate) {
-  CHECK_IN(partials); CHECK_F32(partials); CHECK_IN(g); CHECK_BF16(g);
-  TORCH_CHECK(partials.dim() >= 2 && partials[0].numel() == g.numel(), "splitk_reduce_clear: shape mismatch");
-  TORCH_CHECK(g.numel() % 8 == 0, "splitk_reduce_clear: numel must be a multiple of 8");
+  check_reduce_pair("splitk_reduce_clear", partials, g);
   TORCH_CHECK(ct_splitk_reduce_clear(partials.data_ptr<float>(), (int)partials.size(0), g.numel(), g.data_ptr(),
                                      accumulate ? 1 : 0, cur_stream()) == 0, "splitk_reduce_clear failed");
 }

@@ -406,20 +406,29 @@ bool gemm_w4(at::Tensor A, at::Tensor B, at::Tensor D, int64_t epi, c10::optiona
 extern "C" int ct_gemm_tn2(const void*, long, const void*, long, void*, long, int, int, long, int, int, float*,
                            hipStream_t);
 
+// One weight-gradient problem's operands for gemm_tn2 / gemm_tn_group: bf16 row-major A [K, M] and
+// B [K, N] on the GPU; ``slabs``: out is the fp32 [splits, M, N] partial slabs.
+static void check_tn_problem(const char* who, const at::Tensor& A, const at::Tensor& B, const at::Tensor& out,
+                             long K, int64_t splits, bool slabs) {
+  TORCH_CHECK(A.is_cuda() && B.is_cuda() && out.is_cuda(), who, ": GPU tensors");
+  TORCH_CHECK(A.scalar_type() == at::kBFloat16 && B.scalar_type() == at::kBFloat16, who, ": bf16 operands");
+  TORCH_CHECK(rowmajor_ok(A) && rowmajor_ok(B), who, ": 2-D row-major operands");
+  TORCH_CHECK(A.size(0) == K && B.size(0) == K, who, ": K mismatch");
+  const long M = A.size(1), N = B.size(1);
+  TORCH_CHECK(M < (1L << 31) && N < (1L << 31), who, ": dimension too large");
+  if (slabs)
+    TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() && out.dim() == 3 && out.size(0) == splits &&
+                out.size(1) == M && out.size(2) == N, who, ": fp32 [splits, M, N] slabs");
+}
+
 // out[M,N] = A[K,M]^T @ B[K,N] through the MFMA kernel's weight-gradient layout: splits > 1 ->
 // out is fp32 [splits, M, N] (partial slabs); splits == 1 -> bf16 [M, N] (+)= result.
 static bool gemm_tn2_impl(at::Tensor A, at::Tensor B, at::Tensor out, int64_t splits, bool accumulate,
                           float* biasg) {
-  TORCH_CHECK(A.is_cuda() && B.is_cuda() && out.is_cuda(), "gemm_tn2: GPU tensors");
-  TORCH_CHECK(A.scalar_type() == at::kBFloat16 && B.scalar_type() == at::kBFloat16, "gemm_tn2: bf16 operands");
-  TORCH_CHECK(rowmajor_ok(A) && rowmajor_ok(B), "gemm_tn2: 2-D row-major operands");
+  check_tn_problem("gemm_tn2", A, B, out, A.dim() == 2 ? A.size(0) : -1, splits, splits > 1);
   const long K = A.size(0), M = A.size(1), N = B.size(1);
-  TORCH_CHECK(B.size(0) == K, "gemm_tn2: K mismatch");
   long ldo = 0;
-  if (splits > 1) {
-    TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() && out.dim() == 3 && out.size(0) == splits &&
-                out.size(1) == M && out.size(2) == N, "gemm_tn2: fp32 [splits, M, N] slabs");
-  } else {
+  if (splits <= 1) {
     TORCH_CHECK(out.scalar_type() == at::kBFloat16 && rowmajor_ok(out) && out.size(0) == M && out.size(1) == N,
                 "gemm_tn2: bf16 [M, N] out");
     ldo = out.stride(0);
@@ -456,15 +465,8 @@ bool gemm_tn_group(std::vector<at::Tensor> A, std::vector<at::Tensor> B, std::ve
   std::vector<int> Ms(n), Ns(n);
   const long K = A[0].dim() == 2 ? A[0].size(0) : -1;
   for (size_t i = 0; i < n; ++i) {
-    TORCH_CHECK(A[i].is_cuda() && B[i].is_cuda() && P[i].is_cuda(), "gemm_tn_group: GPU tensors");
-    TORCH_CHECK(A[i].scalar_type() == at::kBFloat16 && B[i].scalar_type() == at::kBFloat16,
-                "gemm_tn_group: bf16 operands");
-    TORCH_CHECK(rowmajor_ok(A[i]) && rowmajor_ok(B[i]), "gemm_tn_group: 2-D row-major operands");
-    TORCH_CHECK(A[i].size(0) == K && B[i].size(0) == K, "gemm_tn_group: K mismatch");
+    check_tn_problem("gemm_tn_group", A[i], B[i], P[i], K, splits, true);
     const long M = A[i].size(1), N = B[i].size(1);
-    TORCH_CHECK(M < (1L << 31) && N < (1L << 31), "gemm_tn_group: dimension too large");
-    TORCH_CHECK(P[i].scalar_type() == at::kFloat && P[i].is_contiguous() && P[i].dim() == 3 && P[i].size(0) == splits &&
-                P[i].size(1) == M && P[i].size(2) == N, "gemm_tn_group: fp32 [splits, M, N] slabs");
     const bool hb = biasg[i].has_value() && biasg[i]->defined();
     if (hb)
       TORCH_CHECK(biasg[i]->is_cuda() && biasg[i]->scalar_type() == at::kFloat && biasg[i]->is_contiguous() &&

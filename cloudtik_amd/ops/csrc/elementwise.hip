@@ -366,6 +366,33 @@ extern "C" int ct_splitk_reduce(const float* P, int S, long n, void* g, int accu
   return 0;
 }
 
+// One thread's 8 elements (vector v of an n-element reduction) for the two multi-entry kernels
+// below, which differ only in how a thread finds its entry: the body of splitk_reduce_kernel
+// without the clear.  (That kernel keeps its own copy: calling this from it moves its register
+// allocation, 60 -> 58 VGPRs, and the kernels' resource tables are held fixed.)
+__device__ __forceinline__ void splitk_reduce_vec(const float* P, int S, long n, bf16_t* g, long v, int accumulate) {
+  float acc[8];
+  if (accumulate) {
+    const u16x8 gv = *reinterpret_cast<const u16x8*>(g + v * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = bf2f(gv[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  }
+#pragma unroll 4
+  for (int s = 0; s < S; ++s) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(P + s * n + v * 8);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(P + s * n + v * 8 + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { acc[j] += a[j]; acc[4 + j] += b[j]; }
+  }
+  u16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = f2bf(acc[j]);
+  *reinterpret_cast<u16x8*>(g + v * 8) = o;
+}
+
 // Two independent reductions in ONE launch (vectors [0, nv) of the first pair, then the second
 // pair's): a weight gradient's fp32 slabs and its bias's [S][N] column-sum partials, which were
 // two back-to-back launches per weight-gradient site (the bias one a few microseconds of launch
@@ -377,29 +404,7 @@ __global__ void __launch_bounds__(256) splitk_reduce2_kernel(Reduce2 r, int accu
   for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < nt; t += (long)gridDim.x * blockDim.x) {
     const int k = t < r.nv[0] ? 0 : 1;
     const long v = k ? t - r.nv[0] : t;
-    const long n = r.nv[k] * 8;
-    const float* P = r.P[k];
-    bf16_t* g = r.g[k];
-    float acc[8];
-    if (accumulate) {
-      const u16x8 gv = *reinterpret_cast<const u16x8*>(g + v * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = bf2f(gv[j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    }
-#pragma unroll 4
-    for (int s = 0; s < r.S[k]; ++s) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(P + s * n + v * 8);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(P + s * n + v * 8 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { acc[j] += a[j]; acc[4 + j] += b[j]; }
-    }
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = f2bf(acc[j]);
-    *reinterpret_cast<u16x8*>(g + v * 8) = o;
+    splitk_reduce_vec(r.P[k], r.S[k], r.nv[k] * 8, r.g[k], v, accumulate);
   }
 }
 
@@ -435,26 +440,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_group_kernel(ReduceGroup r,
       if (t >= r.first[k]) {
         P = r.P[k]; g = r.g[k]; n = r.nv[k] * 8; v = t - r.first[k]; S = r.S[k];
       }
-    float acc[8];
-    if (accumulate) {
-      const u16x8 gv = *reinterpret_cast<const u16x8*>(g + v * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = bf2f(gv[j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    }
-#pragma unroll 4
-    for (int s = 0; s < S; ++s) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(P + s * n + v * 8);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(P + s * n + v * 8 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { acc[j] += a[j]; acc[4 + j] += b[j]; }
-    }
-    u16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = f2bf(acc[j]);
-    *reinterpret_cast<u16x8*>(g + v * 8) = o;
+    splitk_reduce_vec(P, S, n, g, v, accumulate);
   }
 }
 

@@ -578,54 +578,16 @@ __device__ __forceinline__ void nt_epilogue(const NtArgs& a, const f32x4 (&acc)[
   }
 }
 
-// DIAG (timing diagnostics only, wrong results): 1 = no DMA / vmcnt in the K loop (MFMA + LDS
-// reads + barriers), 2 = additionally no barriers (MFMA + LDS reads), 3 = DMA issued but never
-// waited for in the K loop.  LAY: operand layouts (NtLay); 1 = TN weight gradients with
-// blockIdx -> (split, tile).
-template <int EPI, bool BGRAD, int DIAG = 0, int LAY = 0, bool BIASG = false>
-__global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtArgs a) {
+// One 256 x 256 output tile (tm, tn) of K-slice ``split``: lane offsets, accumulators and bias
+// preload, prologue, K loop, drain, epilogue and the bias column sums -- everything a workgroup
+// does once it knows its tile.  ``lds`` is the __global__'s one LDS object.  ``bias_sums``: whether
+// the BIASG column sums of A are wanted (a constant in the one-problem kernel, a per-problem
+// null test in the grouped one).
+template <int EPI, bool BGRAD, int DIAG, int LAY, bool BIASG>
+__device__ __forceinline__ void nt_tile(const NtArgs& a, char* lds, int tm, int tn, int split, int half,
+                                        bool bias_sums) {
   using Ly = NtLay<LAY>;
   constexpr bool SPLIT = LAY == 1;
-  __shared__ __attribute__((aligned(1024))) char lds[2 * NT_BUF];    // 128 KiB, the only LDS object
-  const int tiles_n = a.N / NT_BN;
-  const int tiles = (a.M / NT_BM) * tiles_n;
-  // Staggered grid (NT / NN, a.stagger = H > 0): the first 2H blocks alternate a full tile and
-  // the B0 column half of one of tiles H .. 2H-1, and H blocks at the end do their B1 halves.
-  // The half tiles (about half the time of a full one) put half of the CUs of the first round
-  // half a tile out of phase with the other half for the rest of the grid, so their epilogues
-  // -- store- or VALU-bound with the matrix cores idle -- no longer all hit HBM at once; the
-  // total work is unchanged.  Dispatch order only decides how well it staggers, never what
-  // is computed.
-  int v = blockIdx.x, half = 0;
-  if constexpr (!SPLIT) {
-    const int H = a.stagger;
-    if (H > 0) {
-      if (v < 2 * H) {
-        half = v & 1;
-        v = (v & 1) ? H + (v >> 1) : (v >> 1);
-      } else if (v >= tiles) {
-        half = 2;
-        v = H + (v - tiles);
-      }
-    }
-  }
-  int L = xcd_remap(v, SPLIT ? gridDim.x : tiles);
-  const int split = SPLIT ? L / tiles : 0;
-  L -= split * tiles;
-  // tile order of the blocks that share an XCD (consecutive L): a.group_m > 1 walks group_m
-  // M-tiles for each N-tile (a group_m x (32 / group_m) block of tiles runs at once per XCD,
-  // instead of 2 M-rows x every N-tile), so fewer distinct A / B panels stream into each XCD's
-  // 4 MiB L2 per round
-  int tm, tn;
-  if (!SPLIT && a.group_m > 1) {
-    const int gsz = a.group_m * tiles_n;
-    const int g = L / gsz, r = L - g * gsz;
-    tm = g * a.group_m + r % a.group_m;
-    tn = r / a.group_m;
-  } else {
-    tm = L / tiles_n;
-    tn = L % tiles_n;
-  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: staging bases in SGPRs
   const int wr = wave >> 2, wc = wave & 3;
@@ -638,7 +600,7 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtArgs a) {
   const int nk = kt_q + (split < kt_r ? 1 : 0);
   const long kfirst = SPLIT ? (long)(split * kt_q + min(split, kt_r)) * NT_BK : 0L;
   NtCtx c{a.A, a.B, a.lda, a.ldb, m0, n0, kfirst, lds, wave, lane, wr * 64, wc * 32,
-          0, 0, 0, 0, (BIASG && tn == 0) ? 2 * wc : -1, half};
+          0, 0, 0, 0, (BIASG && bias_sums && tn == 0) ? 2 * wc : -1, half};
   f32x4 accb[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   if constexpr (Ly::AT) {
     c.offa0 = c.offa1 = tn_lane_off(a.lda, wave, lane, true);
@@ -703,6 +665,56 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtArgs a) {
   }
 }
 
+// DIAG (timing diagnostics only, wrong results): 1 = no DMA / vmcnt in the K loop (MFMA + LDS
+// reads + barriers), 2 = additionally no barriers (MFMA + LDS reads), 3 = DMA issued but never
+// waited for in the K loop.  LAY: operand layouts (NtLay); 1 = TN weight gradients with
+// blockIdx -> (split, tile).
+template <int EPI, bool BGRAD, int DIAG = 0, int LAY = 0, bool BIASG = false>
+__global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtArgs a) {
+  constexpr bool SPLIT = LAY == 1;
+  __shared__ __attribute__((aligned(1024))) char lds[2 * NT_BUF];    // 128 KiB, the only LDS object
+  const int tiles_n = a.N / NT_BN;
+  const int tiles = (a.M / NT_BM) * tiles_n;
+  // Staggered grid (NT / NN, a.stagger = H > 0): the first 2H blocks alternate a full tile and
+  // the B0 column half of one of tiles H .. 2H-1, and H blocks at the end do their B1 halves.
+  // The half tiles (about half the time of a full one) put half of the CUs of the first round
+  // half a tile out of phase with the other half for the rest of the grid, so their epilogues
+  // -- store- or VALU-bound with the matrix cores idle -- no longer all hit HBM at once; the
+  // total work is unchanged.  Dispatch order only decides how well it staggers, never what
+  // is computed.
+  int v = blockIdx.x, half = 0;
+  if constexpr (!SPLIT) {
+    const int H = a.stagger;
+    if (H > 0) {
+      if (v < 2 * H) {
+        half = v & 1;
+        v = (v & 1) ? H + (v >> 1) : (v >> 1);
+      } else if (v >= tiles) {
+        half = 2;
+        v = H + (v - tiles);
+      }
+    }
+  }
+  int L = xcd_remap(v, SPLIT ? gridDim.x : tiles);
+  const int split = SPLIT ? L / tiles : 0;
+  L -= split * tiles;
+  // tile order of the blocks that share an XCD (consecutive L): a.group_m > 1 walks group_m
+  // M-tiles for each N-tile (a group_m x (32 / group_m) block of tiles runs at once per XCD,
+  // instead of 2 M-rows x every N-tile), so fewer distinct A / B panels stream into each XCD's
+  // 4 MiB L2 per round
+  int tm, tn;
+  if (!SPLIT && a.group_m > 1) {
+    const int gsz = a.group_m * tiles_n;
+    const int g = L / gsz, r = L - g * gsz;
+    tm = g * a.group_m + r % a.group_m;
+    tn = r / a.group_m;
+  } else {
+    tm = L / tiles_n;
+    tn = L % tiles_n;
+  }
+  nt_tile<EPI, BGRAD, DIAG, LAY, BIASG>(a, lds, tm, tn, split, half, true);
+}
+
 // ---------------------------------------------------------------------------------------
 // Grouped weight-gradient GEMM (TN layout, split-K fp32 slabs): up to NT_GROUP_MAX problems
 // D_i[M_i, N_i] = A_i[K, M_i]^T B_i[K, N_i] that share K (the token count) and one slice count
@@ -711,10 +723,9 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtArgs a) {
 // transformer block fill them together with half the slices, so half the fp32 slab bytes are
 // written and read back, and one launch replaces two.  A workgroup finds its slice, then its
 // tile in the union of the problems' tiles, then the problem (tile-base table); everything
-// after that is gemm_nt_kernel<NT_EPI_F32_SLAB, false, 0, 1, true> on that problem's
-// operands: same staging, phases, fragment reads and K-tile deal.  The bias column sums are a
-// per-problem runtime choice (biasg_i != null).  A separate __global__ so the register
-// allocation of the single-problem instantiations cannot change.
+// after that is nt_tile<NT_EPI_F32_SLAB, false, 0, 1, true> on that problem's operands.  The
+// bias column sums are a per-problem runtime choice (biasg_i != null).  A separate __global__
+// so the register allocation of the single-problem instantiations cannot change.
 constexpr int NT_GROUP_MAX = 4;
 
 struct NtGroupArgs {
@@ -757,58 +768,7 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtGroupArgs g) {
   a.tsplit = g.tsplit;
   const int tiles_n = a.N / NT_BN;
   const int tm = L / tiles_n, tn = L % tiles_n;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-  const long m0 = (long)tm * NT_BM, n0 = (long)tn * NT_BN;
-  const int kt_all = a.K / NT_BK;
-  const int kt_q = kt_all / (int)a.tsplit, kt_r = kt_all % (int)a.tsplit;
-  const int nk = kt_q + (split < kt_r ? 1 : 0);
-  const long kfirst = (long)(split * kt_q + min(split, kt_r)) * NT_BK;
-  NtCtx c{a.A, a.B, a.lda, a.ldb, m0, n0, kfirst, lds, wave, lane, wr * 64, wc * 32,
-          0, 0, 0, 0, (a.biasg != nullptr && tn == 0) ? 2 * wc : -1, 0};
-  f32x4 accb[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  c.offa0 = c.offa1 = tn_lane_off(a.lda, wave, lane, true);
-  c.offb0 = c.offb1 = tn_lane_off(a.ldb, wave, lane, false);
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const long emrow = m0 + wr * 128 + (lane & 15), encol = n0 + wc * 64 + (lane >> 4) * 4;
-  NtEpiPre<4> epre;
-
-  nt_s16x8 fa[2][4][2];
-  nt_s16x8 fb[2][2][2];
-
-#pragma unroll
-  for (int v = -6; v < -2; ++v) nt_stage_v<LAY>(c, v);
-  if (nk > 1) {
-    nt_stage_v<LAY>(c, -2);
-    nt_stage_v<LAY>(c, -1);
-    nt_vm<8>();
-  } else {
-    nt_vm<4>();
-  }
-  nt_bar();
-  if (wr == 1) nt_bar();                                 // group 1 runs one barrier behind
-
-  int t = 0;
-  for (; t < nk - 2; ++t) nt_ktile<0, 0, LAY, true>(c, t, acc, fa, fb, accb);
-  if (nk >= 2) {
-    nt_ktile<1, 0, LAY, true>(c, t, acc, fa, fb, accb);
-    ++t;
-  }
-  nt_ktile<2, 0, LAY, true>(c, t, acc, fa, fb, accb);
-  if (wr == 0) nt_bar();                                 // equal barrier counts for both groups
-
-  nt_epilogue<NT_EPI_F32_SLAB, false, 4>(a, acc, emrow, encol, lane, split, epre, 0);
-  if (c.biasw >= 0 && lane < 16) {
-#pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2)
-      a.biasg[(long)split * a.M + m0 + wr * 128 + 16 * (c.biasw + t2) + lane] = accb[t2][0];
-  }
+  nt_tile<EPI, BGRAD, DIAG, LAY, BIASG>(a, lds, tm, tn, split, 0, a.biasg != nullptr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1329,11 +1289,23 @@ extern "C" int ct_gemm_nt(const void* A, long lda, const void* B, long ldb, void
 // bf16 out (+)= result (accumulate), row stride ldo.  biasg (optional, fp32 [splits][M]): the
 // column sums of A per split (the bias gradient when A is dY).  Nonzero (nothing launched)
 // when the shape / alignment is unsupported.
+// One TN problem's operands, for ct_gemm_tn2 and ct_gemm_tn_group: 1 = M, N not in whole tiles,
+// 3 = leading dimensions or pointers the 16-byte DMA cannot take, 0 = fine.
+static int tn_problem_check(const void* A, long lda, const void* B, long ldb, int M, int N) {
+  if (M <= 0 || N <= 0 || M % NT_BM || N % NT_BN) return 1;
+  if (lda % 8 || ldb % 8 || lda < M || ldb < N || !A || !B || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return 3;
+  return 0;
+}
+
+// The shared token count: whole K-tiles, at least one per slice.
+static bool tn_k_ok(long K, int splits) { return K % NT_BK == 0 && K / NT_BK >= splits && K <= (1L << 30); }
+
 extern "C" int ct_gemm_tn2(const void* A, long lda, const void* B, long ldb, void* out, long ldo, int M, int N,
                            long K, int splits, int accumulate, float* biasg, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || splits < 1 || M % NT_BM || N % NT_BN) return 1;
-  if (K % NT_BK || K / NT_BK < splits || K > (1L << 30)) return 2;
-  if (lda % 8 || ldb % 8 || lda < M || ldb < N || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return 3;
+  const int rc = tn_problem_check(A, lda, B, ldb, M, N);
+  if (rc == 1 || K <= 0 || splits < 1) return 1;
+  if (!tn_k_ok(K, splits)) return 2;
+  if (rc) return rc;
   if (((uintptr_t)out & 15) || (splits == 1 && (ldo % 8 || ldo < N))) return 4;
   const long blocks = (long)(M / NT_BM) * (N / NT_BN) * splits;
   if (blocks > (1L << 30)) return 5;
@@ -1363,15 +1335,12 @@ extern "C" int ct_gemm_tn_group(int nprob, const void* const* A, const long* lda
                                 const long* ldb, float* const* P, float* const* biasg, const int* M, const int* N,
                                 long K, int splits, hipStream_t stream) {
   if (nprob < 1 || nprob > NT_GROUP_MAX || splits < 2) return 1;
-  if (K <= 0 || K % NT_BK || K / NT_BK < splits || K > (1L << 30)) return 2;
+  if (K <= 0 || !tn_k_ok(K, splits)) return 2;
   NtGroupArgs g{};
   long tiles = 0;
   for (int i = 0; i < NT_GROUP_MAX; ++i) g.tile_base[i] = 0x7fffffff;
   for (int i = 0; i < nprob; ++i) {
-    if (M[i] <= 0 || N[i] <= 0 || M[i] % NT_BM || N[i] % NT_BN) return 1;
-    if (lda[i] % 8 || ldb[i] % 8 || lda[i] < M[i] || ldb[i] < N[i] || !A[i] || !B[i] || ((uintptr_t)A[i] & 15) ||
-        ((uintptr_t)B[i] & 15))
-      return 3;
+    if (const int rc = tn_problem_check(A[i], lda[i], B[i], ldb[i], M[i], N[i])) return rc;
     if (!P[i] || ((uintptr_t)P[i] & 15) || (biasg[i] && ((uintptr_t)biasg[i] & 3))) return 4;
     g.A[i] = (const bf16_t*)A[i];
     g.B[i] = (const bf16_t*)B[i];

@@ -4,8 +4,11 @@ buffer ("gradient-accumulation fusion").
 With PyTorch's stock ``F.linear`` backward, dW is produced into a fresh tensor and then
 ``AccumulateGrad`` adds it into ``param.grad`` -- one extra read-read-write pass over every
 weight per step (the flat buffer of train.optim.FlatParamSpace is pre-set as ``.grad``).
-Here the backward issues ``grad.addmm_(dY^T, X)`` instead: hipBLASLt's beta=1 epilogue does
-the accumulation inside the GEMM, and no extra elementwise kernel runs.  Because autograd
+Here the backward calls ``issue_wgrads`` instead, the one entry every weight gradient goes
+through (this layer's and the transformer blocks'): on the side stream or in line, a lone
+gradient through ``wgrad_accumulate`` -- the MFMA TN kernel, split-K fp32 slabs and a reduce
+that adds them into the bf16 gradient; hipBLASLt where a shape is outside its tiling -- and the
+gradients of one block through ``wgrad_accumulate_group``, one launch for all.  Because autograd
 then never sees a weight gradient, the data-parallel bucketer is notified explicitly
 (``param._ct_grad_ready``, installed by parallel.ddp.GradBucketer).
 """
@@ -134,37 +137,60 @@ def side_grad_stream():
     return s
 
 
+def _on_side_stream(issue, operands, enabled: bool) -> bool:
+    """Run ``issue()`` on the gradient side stream, after everything queued on the current
+    stream (dY / X produced, grad zeroed), and keep ``operands`` alive until it has run there;
+    False (nothing issued) when ``enabled`` is False or there is no GPU."""
+    s = side_grad_stream() if enabled else None
+    if s is None:
+        return False
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        issue()
+    for t in operands:
+        t.record_stream(s)
+    return True
+
+
 def wgrad_on_side_stream(g: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor,
                          dbias: Optional[torch.Tensor] = None, enabled: bool = True) -> bool:
     """Issue ``g += dy2^T x2`` (and ``dbias += column sums of dy2``) on the gradient side
     stream; False (nothing issued) when ``enabled`` is False or there is no GPU."""
-    s = side_grad_stream() if (g.is_cuda and enabled) else None
-    if s is None:
-        return False
-    cur = torch.cuda.current_stream()
-    s.wait_stream(cur)                       # dY / X produced (and grad zeroed) on the main stream
-    with torch.cuda.stream(s):
-        wgrad_accumulate(g, dy2, x2, dbias)
-    dy2.record_stream(s)
-    x2.record_stream(s)
-    return True
+    return _on_side_stream(lambda: wgrad_accumulate(g, dy2, x2, dbias), (dy2, x2), g.is_cuda and enabled)
 
 
 def wgrad_group_on_side_stream(items, enabled: bool = True) -> bool:
-    """``wgrad_accumulate_group(items)`` on the gradient side stream (the grouped form of
-    ``wgrad_on_side_stream``: the same ordering and lifetime handling for every operand);
-    False (nothing issued) when ``enabled`` is False or there is no GPU."""
-    s = side_grad_stream() if (enabled and all(it[0].is_cuda for it in items)) else None
-    if s is None:
-        return False
-    cur = torch.cuda.current_stream()
-    s.wait_stream(cur)
-    with torch.cuda.stream(s):
-        wgrad_accumulate_group(items)
-    for _g, dy2, x2, _db in items:
-        dy2.record_stream(s)
-        x2.record_stream(s)
-    return True
+    """``wgrad_accumulate_group(items)`` on the gradient side stream; False (nothing issued)
+    when ``enabled`` is False or there is no GPU."""
+    return _on_side_stream(lambda: wgrad_accumulate_group(items), [t for it in items for t in it[1:3]],
+                           enabled and all(it[0].is_cuda for it in items))
+
+
+def grad_ready(*params) -> None:
+    """Tell the data-parallel bucketer that these parameters' gradients have been issued."""
+    for p in params:
+        cb = getattr(p, "_ct_grad_ready", None)
+        if cb is not None:
+            cb(p)
+
+
+def issue_wgrads(items) -> None:
+    """Accumulate the weight gradient of every ``(param, dy2, x2, bias_param_or_None)`` of
+    ``items`` into ``param.grad`` (flat, one routing for all) and, with a bias, the column sums
+    of dy2 into ``bias.grad``: on the side stream when the weights are routed there, else in
+    line; one item through ``wgrad_accumulate``, several (one block's, same tokens) through
+    ``wgrad_accumulate_group``.  Then every weight and bias is reported ready, in order."""
+    args = [(p.grad, dy2, x2, b.grad if b is not None else None) for p, dy2, x2, b in items]
+    side = wgrad_side(items[0][0])
+    if len(args) == 1:
+        if not wgrad_on_side_stream(*args[0], enabled=side):
+            wgrad_accumulate(*args[0])
+    elif not wgrad_group_on_side_stream(args, enabled=side):
+        wgrad_accumulate_group(args)
+    for p, _dy2, _x2, b in items:
+        grad_ready(p)
+        if b is not None:
+            grad_ready(b)
 
 
 def splitk_factor(T: int, N: int, K: int) -> int:
@@ -181,18 +207,17 @@ def splitk_factor(T: int, N: int, K: int) -> int:
     return S
 
 
-def tn2_splits(T: int, N: int, K: int, cus: int = 256) -> int:
-    """Split factor for the MFMA wgrad kernel (any S: the kernel deals the T / 64 K-tiles out
-    over the slices).  Modelled time = K loop + fp32 slab round trip:
+def _tn2_choose(T: int, tiles: int, nk: int, cus: int) -> int:
+    """The MFMA wgrad kernel's slice count for ``tiles`` 256 x 256 output tiles holding ``nk``
+    elements in all (any S: the kernel deals the T / 64 K-tiles out over the slices).
+    Modelled time = K loop + fp32 slab round trip:
       loop(S) = t_full * waves(S) * cus / (tiles * S), waves = ceil(tiles * S / cus), with
-      t_full the loop time at a perfect spread (2 N K T at ~1.3 PF/s, measured K-loop rate);
+      t_full the loop time at a perfect spread (2 nk T at ~1.3 PF/s, measured K-loop rate);
       slab(S) = S * tiles * 256 KiB * 2 (written, read back by the reduce) at ~5 TB/s (0 at S=1).
-    BERT-large: qkv 48 tiles -> 5 (240 workgroups, one wave; 16 power-of-two slices cost 3x the
-    slab bytes), proj 16 tiles -> 16, FFN 64 tiles -> 4.  >= 512 tokens per slice."""
-    tiles = (N // 256) * (K // 256)
+    >= 512 tokens per slice."""
     if tiles <= 0 or T % 64:
         return 1
-    t_full = 2.0 * N * K * T / 1.3e15
+    t_full = 2.0 * nk * T / 1.3e15
     best, best_cost = 1, None
     for S in range(1, 33):
         if S > 1 and (T // S < 512 or T // 64 < S):
@@ -202,6 +227,14 @@ def tn2_splits(T: int, N: int, K: int, cus: int = 256) -> int:
         if best_cost is None or cost < best_cost * (1 - 1e-9):
             best, best_cost = S, cost
     return best
+
+
+def tn2_splits(T: int, N: int, K: int, cus: int = 256) -> int:
+    """Split factor for one weight gradient dW[N, K] on the MFMA wgrad kernel (``_tn2_choose``).
+    BERT-large: qkv 48 tiles -> 5 (240 workgroups, one wave; 16 power-of-two slices cost 3x the
+    slab bytes), proj 16 tiles -> 16, FFN 64 tiles -> 4.  Counts whole tiles only: the caller
+    checks N and K against the tiling."""
+    return _tn2_choose(T, (N // 256) * (K // 256), N * K, cus)
 
 
 def tn2_group_splits(T: int, shapes, cus: int = 256) -> int:
@@ -210,39 +243,42 @@ def tn2_group_splits(T: int, shapes, cus: int = 256) -> int:
     BERT-large (T = 32768): Wo + Wqkv 64 tiles -> 4, W2 + W1 128 tiles -> 2.  1 when a shape is
     outside the kernel's tiling."""
     shapes = list(shapes)
-    if not shapes or T % 64 or any(N <= 0 or K <= 0 or N % 256 or K % 256 for N, K in shapes):
+    if not shapes or any(N <= 0 or K <= 0 or N % 256 or K % 256 for N, K in shapes):
         return 1
-    tiles = sum((N // 256) * (K // 256) for N, K in shapes)
-    t_full = 2.0 * sum(N * K for N, K in shapes) * T / 1.3e15
-    best, best_cost = 1, None
-    for S in range(1, 33):
-        if S > 1 and (T // S < 512 or T // 64 < S):
-            continue
-        waves = -(-tiles * S // cus)
-        cost = t_full * waves * cus / (tiles * S) + (S * tiles * 262144 * 2 / 5e12 if S > 1 else 0.0)
-        if best_cost is None or cost < best_cost * (1 - 1e-9):
-            best, best_cost = S, cost
-    return best
+    return _tn2_choose(T, sum((N // 256) * (K // 256) for N, K in shapes), sum(N * K for N, K in shapes), cus)
 
 
 _GROUP_MAX = 4      # problems per grouped GEMM launch, entries per grouped reduce launch
 
 
+def _mfma_tn_ok(g: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor) -> bool:
+    """Whether ``g += dy2^T x2`` takes the MFMA TN kernel: bf16 on a GPU, widths in whole
+    256 x 256 tiles, tokens in whole 64-row K-tiles."""
+    return (_HIP_WGRAD and g.is_cuda and g.dtype == torch.bfloat16 and dy2.dtype == torch.bfloat16
+            and dy2.shape[1] % 256 == 0 and x2.shape[1] % 256 == 0 and dy2.shape[0] % 64 == 0)
+
+
+def _bias_fused(dbias: Optional[torch.Tensor]) -> bool:
+    """Whether this bias gradient comes out of the weight-gradient GEMM (all-ones MFMA)."""
+    return (_WGRAD_BIAS_FUSE and dbias is not None and dbias.dtype == torch.bfloat16
+            and dbias.is_contiguous())
+
+
 def _group_qualifies(items) -> bool:
-    """The conditions of ``wgrad_accumulate``'s MFMA path for every problem, one token count
-    and one device for all, and gradients the grouped reduce can write (contiguous, 16-byte
-    aligned)."""
-    if not (_HIP_WGRAD and 2 <= len(items) <= _GROUP_MAX):
+    """``_mfma_tn_ok`` for every problem, over one token count and on one device.  On top of
+    it, what only the grouped entries need: a group always ends in the grouped reduce, which
+    takes each g as a raw pointer to a dense [N, K] array and refuses one that is not 16-byte
+    aligned (a lone gradient may be unsplit, written by the GEMM itself through g's stride);
+    and a bad x2 dtype falls back here, to raise from the lone entry as it always has."""
+    if not 2 <= len(items) <= _GROUP_MAX:
         return False
     T, dev = items[0][1].shape[0], items[0][0].device
     for g, dy2, x2, _db in items:
         if dy2.dim() != 2 or x2.dim() != 2 or dy2.shape[0] != T or x2.shape[0] != T:
             return False
-        N, K = dy2.shape[1], x2.shape[1]
-        if not (g.is_cuda and g.device == dev and g.dtype == torch.bfloat16 and dy2.dtype == torch.bfloat16
-                and x2.dtype == torch.bfloat16 and N % 256 == 0 and K % 256 == 0 and T % 64 == 0):
+        if not (_mfma_tn_ok(g, dy2, x2) and g.device == dev and x2.dtype == torch.bfloat16):
             return False
-        if tuple(g.shape) != (N, K) or not g.is_contiguous() or g.data_ptr() % 16:
+        if tuple(g.shape) != (dy2.shape[1], x2.shape[1]) or not g.is_contiguous() or g.data_ptr() % 16:
             return False
     return True
 
@@ -263,8 +299,8 @@ def wgrad_accumulate_group(items) -> None:
         return
     from cloudtik_amd import ops
     C = ops.require_native()
-    fuse = [(_WGRAD_BIAS_FUSE and db is not None and db.dtype == torch.bfloat16 and db.is_contiguous()
-             and db.data_ptr() % 16 == 0) for _g, _dy2, _x2, db in items]
+    # the grouped reduce refuses a misaligned bias gradient: that one takes the column-sum kernel
+    fuse = [_bias_fused(db) and db.data_ptr() % 16 == 0 for _g, _dy2, _x2, db in items]
     sizes = [S * dy2.shape[1] * x2.shape[1] for _g, dy2, x2, _db in items]
     bsizes = [S * it[1].shape[1] if f else 0 for it, f in zip(items, fuse)]
     ws = torch.empty(sum(sizes) + sum(bsizes), device=items[0][0].device, dtype=torch.float32)
@@ -308,14 +344,12 @@ def wgrad_accumulate(g: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor,
     the GPU, plus a column-sum kernel for the bias."""
     T, N = dy2.shape
     K = x2.shape[1]
-    if (_HIP_WGRAD and g.is_cuda and g.dtype == torch.bfloat16 and dy2.dtype == torch.bfloat16
-            and N % 256 == 0 and K % 256 == 0 and T % 64 == 0):
+    if _mfma_tn_ok(g, dy2, x2):
         from cloudtik_amd import ops
         C = ops.require_native()
         S = tn2_splits(T, N, K)
         dy2c, x2c = dy2.contiguous(), x2.contiguous()
-        fuse_bias = (_WGRAD_BIAS_FUSE and dbias is not None and dbias.dtype == torch.bfloat16
-                     and dbias.is_contiguous())
+        fuse_bias = _bias_fused(dbias)
         bP = torch.empty(S, N, device=g.device, dtype=torch.float32) if fuse_bias else None
         out = g if S == 1 else torch.empty(S, N, K, device=g.device, dtype=torch.float32)
         ok = (C.gemm_tn2_bias(dy2c, x2c, out, S, S == 1, bP) if fuse_bias
@@ -371,11 +405,7 @@ class _LinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             g = Wp.grad
             if g is not None and getattr(Wp, "_ct_flat_grad", False) and g.dtype == dy.dtype:
-                if not wgrad_on_side_stream(g, dy2, x2, enabled=wgrad_side(Wp)):
-                    wgrad_accumulate(g, dy2, x2)
-                cb = getattr(Wp, "_ct_grad_ready", None)
-                if cb is not None:
-                    cb(Wp)
+                issue_wgrads([(Wp, dy2, x2, None)])
             else:
                 dW = torch.matmul(dy2.t(), x2)
         db = dy2.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None

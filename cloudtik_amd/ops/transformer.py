@@ -6,7 +6,7 @@ Each block is ONE autograd node with a hand-written backward, so that
   (``dx = addmm(d_residual, d_qkv, W_qkv)``: hipBLASLt beta=1) instead of by the autograd
   engine's separate elementwise add (2 x [tokens, hidden] per layer);
 * weight gradients are accumulated by the wgrad GEMMs straight into the flat gradient
-  buffer (``grad.addmm_``) and every LayerNorm / bias gradient is accumulated by the
+  buffer (``ops.linear.issue_wgrads``) and every LayerNorm / bias gradient is accumulated by the
   LayerNorm / bias-GELU backward kernels into the same buffer -- no AccumulateGrad kernels;
 * the data-parallel bucketer is told the moment a parameter's gradient has been issued
   (``param._ct_grad_ready``), so RCCL all-reduces overlap the rest of backward.
@@ -25,8 +25,8 @@ import os
 
 import torch
 
-from cloudtik_amd.ops.linear import (wgrad_accumulate, wgrad_accumulate_group, wgrad_group_enabled,
-                                     wgrad_group_on_side_stream, wgrad_on_side_stream, wgrad_side)
+from cloudtik_amd.ops.linear import grad_ready as _ready
+from cloudtik_amd.ops.linear import issue_wgrads, wgrad_group_enabled, wgrad_side
 
 
 def _C():
@@ -194,27 +194,6 @@ def _flat(p) -> bool:
     return p.grad is not None and getattr(p, "_ct_flat_grad", False)
 
 
-def _ready(*params):
-    for p in params:
-        cb = getattr(p, "_ct_grad_ready", None)
-        if cb is not None:
-            cb(p)
-
-
-def _wgrad(p, dy2, x2, bias=None):
-    """dW = dy2^T x2, accumulated into the flat buffer when possible.  With ``bias`` (a flat
-    parameter), its gradient -- the column sums of dy2 -- comes out of the same GEMM."""
-    if _flat(p):
-        db = bias.grad if bias is not None else None
-        if not wgrad_on_side_stream(p.grad, dy2, x2, db, enabled=wgrad_side(p)):
-            wgrad_accumulate(p.grad, dy2, x2, db)
-        _ready(p)
-        if bias is not None:
-            _ready(bias)
-        return None
-    return dy2.t() @ x2
-
-
 def _group_ok(pa, pb, pair) -> bool:
     """Whether the weight gradients of ``pa`` and ``pb`` (one block, same tokens) go out as one
     grouped launch: both flat, same routing, grouping enabled for that routing and ``pair``."""
@@ -222,16 +201,15 @@ def _group_ok(pa, pb, pair) -> bool:
             and wgrad_group_enabled(wgrad_side(pa), pair))
 
 
-def _wgrad_group(items):
-    """``_wgrad(p, dy2, x2, bias)`` for every ``(p, dy2, x2, bias)`` of ``items`` (all flat, one
-    routing: ``_group_ok``) as one grouped split-K GEMM + one grouped reduce."""
-    args = [(p.grad, dy2, x2, b.grad if b is not None else None) for p, dy2, x2, b in items]
-    if not wgrad_group_on_side_stream(args, enabled=wgrad_side(items[0][0])):
-        wgrad_accumulate_group(args)
-    for p, _dy2, _x2, b in items:
-        _ready(p)
-        if b is not None:
-            _ready(b)
+def _wgrad(p, dy2, x2, bias=None, held=None):
+    """dW = dy2^T x2, accumulated into the flat buffer when possible.  With ``bias`` (a flat
+    parameter), its gradient -- the column sums of dy2 -- comes out of the same GEMM.  ``held``:
+    the block's earlier ``(p, dy2, x2, bias)`` that waited for this one (``_group_ok``); the two
+    go out as one grouped split-K GEMM + one grouped reduce."""
+    if _flat(p):
+        issue_wgrads([held, (p, dy2, x2, bias)] if held is not None else [(p, dy2, x2, bias)])
+        return None
+    return dy2.t() @ x2
 
 
 def _vec_grad_out(p):
@@ -293,8 +271,8 @@ class _AttnBlockFn(torch.autograd.Function):
         _ready(*[p for p, f in ((g1, fg1), (b1, fb1), (bo, fbo)) if f])
         o2 = o.view(B * S, H)
         # grouped: the Wo gradient waits for dqkv and goes out with the Wqkv one (one launch)
-        hold_wo = _group_ok(Wo, Wqkv, "attn")
-        dWo = None if hold_wo else _wgrad(Wo, da, o2)
+        held = (Wo, da, o2, None) if _group_ok(Wo, Wqkv, "attn") else None
+        dWo = None if held is not None else _wgrad(Wo, da, o2)
         do = _stream_mm("do", da, Wo, True, side=wgrad_side(Wo))
         if do is None:
             do = torch.mm(da, Wo)
@@ -305,19 +283,12 @@ class _AttnBlockFn(torch.autograd.Function):
         C.attn_bwd(v5[:, :, 0], v5[:, :, 1], v5[:, :, 2], o, do, d5[:, :, 0], d5[:, :, 1], d5[:, :, 2],
                    kb if has_kb else None, lse, scale, p_attn, seed_a, off_a, False)
         dbq, fbq = _vec_grad_out(bqkv)
-        if fbq and _flat(Wqkv):
-            if hold_wo:
-                dWqkv = _wgrad_group([(Wo, da, o2, None), (Wqkv, dqkv, x2, bqkv)])
-            else:
-                dWqkv = _wgrad(Wqkv, dqkv, x2, bias=bqkv)      # bias grad fused into the wgrad GEMM
-        else:
+        bias_in_wgrad = fbq and _flat(Wqkv)                        # bias grad fused into the wgrad GEMM
+        if not bias_in_wgrad:
             C.bias_act_bwd_into(dqkv, dqkv, None, 0, dbq, False)   # column sum of dqkv
             if fbq:
                 _ready(bqkv)
-            if hold_wo:
-                dWqkv = _wgrad_group([(Wo, da, o2, None), (Wqkv, dqkv, x2, None)])
-            else:
-                dWqkv = _wgrad(Wqkv, dqkv, x2)
+        dWqkv = _wgrad(Wqkv, dqkv, x2, bqkv if bias_in_wgrad else None, held)
         dx = _stream_mm("dx_attn", dqkv, Wqkv, True, out=ds, side=wgrad_side(Wqkv))
         if dx is None:
             dx = ds.addmm_(dqkv, Wqkv)    # residual grad fused: in-place beta=1 epilogue, no C copy
@@ -371,35 +342,22 @@ class _FFNBlockFn(torch.autograd.Function):
             df = ds
         _ready(*[p for p, f in ((g2, fg2), (b2, fb2), (b2f, fb2f)) if f])
         # grouped: the W2 gradient waits for dz and goes out with the W1 one (one launch)
-        hold_w2 = _group_ok(W2, W1, "ffn")
-        dW2 = None if hold_w2 else _wgrad(W2, df, h)
+        held = (W2, df, h, None) if _group_ok(W2, W1, "ffn") else None
+        dW2 = None if held is not None else _wgrad(W2, df, h)
         db1f, fb1f = _vec_grad_out(b1f)
         bias_in_wgrad = _FFN_BGRAD_IN_WGRAD and dgelu and fb1f and _flat(W1)
         dz = (_fused_ffn_dgrad(C, df.contiguous(), W2, z, zbias, None if bias_in_wgrad else db1f, dgelu)
               if _FUSED_FFN_DGRAD else None)
-        if dz is not None and bias_in_wgrad:
-            if hold_w2:
-                dW1 = _wgrad_group([(W2, df, h, None), (W1, dz, x2, b1f)])
-            else:
-                dW1 = _wgrad(W1, dz, x2, bias=b1f)     # bias gradient fused into the wgrad GEMM
-            dx = _stream_mm("dx_ffn", dz, W1, True, out=ds, side=wgrad_side(W1))
-            if dx is None:
-                dx = ds.addmm_(dz, W1)
-            return (dx.view(B, S, H), dW1, None, dW2, None if fb2f else db2f,
-                    None if fg2 else dg2, None if fb2 else db2, None, None, None, None)
-        bias_in_wgrad = False
+        bias_in_wgrad = bias_in_wgrad and dz is not None   # else the sums are taken right here
         if dz is None and dgelu:
             dz = torch.mm(df, W2).mul_(z)
             db1f.add_(dz.float().sum(0).to(db1f.dtype))
         elif dz is None:
             dh = torch.mm(df, W2)
             dz = C.bias_act_bwd_into(dh, z, zbias, 1, db1f, True)
-        if fb1f:
+        if fb1f and not bias_in_wgrad:
             _ready(b1f)
-        if hold_w2:
-            dW1 = _wgrad_group([(W2, df, h, None), (W1, dz, x2, None)])
-        else:
-            dW1 = _wgrad(W1, dz, x2)
+        dW1 = _wgrad(W1, dz, x2, b1f if bias_in_wgrad else None, held)
         dx = _stream_mm("dx_ffn", dz, W1, True, out=ds, side=wgrad_side(W1))
         if dx is None:
             dx = ds.addmm_(dz, W1)

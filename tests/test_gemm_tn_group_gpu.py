@@ -159,6 +159,41 @@ def test_splitk_reduce_group_exact(count, accumulate):
         assert torch.equal(g, _ascending_sum(P, base if accumulate else None))
 
 
+@pytest.mark.parametrize("accumulate", [False, True])
+@pytest.mark.parametrize("numel", [8, 8 * 257])         # one vector; one vector past a full workgroup
+@pytest.mark.parametrize("S", [1, 3, 4, 5])             # around the slice loop's unroll of 4
+def test_reduce_kernels_agree_bit_for_bit(S, numel, accumulate):
+    """splitk_reduce, splitk_reduce2 (as either half), splitk_reduce_group (as any entry) and
+    splitk_reduce_clear on one (P, g): each equals the ascending-order fp32 sum exactly, and the
+    clear form leaves P all zero."""
+    C = _C()
+    gen = torch.Generator(device="cuda").manual_seed(100 * S + numel)
+    P = torch.randn(S, numel, device="cuda", generator=gen)
+    g0 = _rand(numel, seed=70 + S)
+    want = _ascending_sum(P, g0 if accumulate else None)
+    other_P = torch.randn(2, 16, device="cuda", generator=gen)      # the launch's other entries
+    fresh = lambda: (g0.clone(), _rand(16, seed=71))
+
+    g, _ = fresh()
+    C.splitk_reduce(P, g, accumulate)
+    assert torch.equal(g, want)
+    for first in (True, False):
+        g, o = fresh()
+        C.splitk_reduce2(*((P, g, other_P, o) if first else (other_P, o, P, g)), accumulate)
+        assert torch.equal(g, want)
+    for slot in range(4):
+        g, _ = fresh()
+        Ps, gs = [other_P.clone() for _ in range(4)], [fresh()[1] for _ in range(4)]
+        Ps[slot], gs[slot] = P, g
+        C.splitk_reduce_group(Ps, gs, accumulate)
+        assert torch.equal(g, want)
+    g, _ = fresh()
+    Pc = P.clone()
+    C.splitk_reduce_clear(Pc, g, accumulate)
+    assert torch.equal(g, want)
+    assert Pc.count_nonzero().item() == 0
+
+
 def test_wgrad_accumulate_group_matches_separate_calls():
     """The grouped accumulate and the two per-problem calls are both within the slab tolerance
     of the fp32 reference (not bitwise equal: the partial counts differ); the grouped call is

@@ -569,6 +569,129 @@ def test_bert_layer_blocks_match_composed(cuda, p, fused, fused_fwd, stream, mon
         assert set(stream_sites) == {"qkv", "wo", "ffn2", "do", "dx_attn", "dx_ffn"}, stream_sites
 
 
+_ATTN_PAIR = ((256, 256), (768, 256))          # Wo + Wqkv
+_FFN_PAIR = ((256, 1024), (1024, 256))         # W2 + W1
+_GROUPED_BLOCK_REF = {}
+
+
+def _grouped_block_case(cuda, leave_out=()):
+    """One BertLayer at T = 8 x 128 = 1024 tokens (the fewest at which the slice chooser gives
+    both pairs 2 slices, so both take the grouped kernel), its inputs, and the composed-op
+    reference (y, dx, flat gradient, gradients of the ``leave_out`` parameters), computed once
+    per ``leave_out`` and shared by the cases below."""
+    case = _GROUPED_BLOCK_REF.get(leave_out)
+    if case is not None:
+        return case
+    from cloudtik_amd.models.bert import BertConfig, BertLayer
+    from cloudtik_amd.ops import transformer as T
+    from cloudtik_amd.train.optim import FlatParamSpace
+    cfg = BertConfig.tiny(hidden_size=256, num_attention_heads=4, intermediate_size=1024,
+                          hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
+    torch.manual_seed(0)
+    lay = BertLayer(cfg, device=cuda, dtype=torch.bfloat16)
+    named = [(n, q) for n, q in lay.named_parameters() if n not in leave_out]
+    loose = [q for n, q in lay.named_parameters() if n in leave_out]
+    sp = FlatParamSpace([q for _, q in named], names=[n for n, _ in named])
+    x = torch.randn(8, 128, 256, device=cuda, dtype=torch.bfloat16, requires_grad=True)
+    kb = torch.zeros(8, 128, device=cuda)
+    kb[1, 100:] = -10000.0
+    dy = torch.randn(8, 128, 256, device=cuda, dtype=torch.bfloat16)
+    orig = T.blocks_supported
+    T.blocks_supported = lambda *a, **k: False
+    try:
+        ops.manual_seed(5)
+        y = lay(x, kb)
+        y.backward(dy)
+    finally:
+        T.blocks_supported = orig
+    ref = (y.detach().clone(), x.grad.clone(), sp.grad.clone().float(), [q.grad.clone() for q in loose])
+    case = _GROUPED_BLOCK_REF[leave_out] = (lay, sp, loose, x, kb, dy, ref)
+    return case
+
+
+def _run_grouped_block(case, monkeypatch, side, group_env, bgrad):
+    """Forward + block backward under one setting; returns (y, dx, flat gradient, loose
+    gradients, the pairs ``wgrad_accumulate_group`` was given, the native grouped GEMM's
+    results)."""
+    import importlib
+    from cloudtik_amd.ops import transformer as T
+    linear = importlib.import_module("cloudtik_amd.ops.linear")     # (ops.linear is also a function)
+    lay, sp, loose, x, kb, dy, _ref = case
+    linear.use_wgrad_side_stream(lay, side)
+    monkeypatch.setattr(linear, "_WGRAD_GROUP_ENV", group_env)
+    monkeypatch.setattr(T, "_FFN_BGRAD_IN_WGRAD", bgrad)
+    groups, native = [], []
+    real_group, C = linear.wgrad_accumulate_group, ops.require_native()
+    real_native = C.gemm_tn_group
+
+    def spy_group(items):
+        groups.append((tuple(tuple(it[0].shape) for it in items), tuple(it[3] is not None for it in items)))
+        real_group(items)
+
+    def spy_native(*a):
+        native.append(real_native(*a))
+        return native[-1]
+
+    monkeypatch.setattr(linear, "wgrad_accumulate_group", spy_group)
+    monkeypatch.setattr(C, "gemm_tn_group", spy_native)
+    sp.zero_grad()
+    x.grad = None
+    for q in loose:
+        q.grad = None
+    ops.manual_seed(5)
+    y = lay(x, kb)
+    y.backward(dy)
+    torch.cuda.synchronize()
+    return y.detach(), x.grad.clone(), sp.grad.clone().float(), [q.grad.clone() for q in loose], groups, native
+
+
+@pytest.mark.parametrize("bgrad", [True, False])
+@pytest.mark.parametrize("group_env", [None, "0", "attn", "ffn"])
+@pytest.mark.parametrize("side", [True, False])
+def test_block_backward_on_the_grouped_path(cuda, monkeypatch, side, group_env, bgrad):
+    """The block backwards at a token count where the pairs really group: the grouped kernel
+    runs for exactly the pairs CLOUDTIK_AMD_WGRAD_GROUP names (both by default), on either
+    routing, with FFN1's bias gradient riding in the grouped GEMM (``bgrad``) or coming from
+    the data-gradient epilogue; gradients match the composed path within
+    test_bert_layer_blocks_match_composed's bounds and are bit-equal between two runs -- all
+    but FFN1's bias gradient on the epilogue route, whose fp32 column sums are float atomics
+    (eight per column here, in no fixed order), so its last bf16 bit is not pinned."""
+    case = _grouped_block_case(cuda)
+    y_ref, dx_ref, g_ref, _ = case[-1]
+    y, dx, g, _, groups, native = _run_grouped_block(case, monkeypatch, side, group_env, bgrad)
+    want = {None: [(_FFN_PAIR, (False, bgrad)), (_ATTN_PAIR, (False, True))], "0": [],
+            "attn": [(_ATTN_PAIR, (False, True))], "ffn": [(_FFN_PAIR, (False, bgrad))]}[group_env]
+    assert groups == want                      # backward order: the FFN block, then attention
+    assert native == [True] * len(want)
+    assert _rel(y, y_ref) < 1e-2
+    assert _rel(dx, dx_ref) < 2e-2
+    assert _rel(g, g_ref) < 2e-2
+    y2, dx2, g2, _, groups2, _ = _run_grouped_block(case, monkeypatch, side, group_env, bgrad)
+    assert groups2 == want
+    assert torch.equal(y, y2) and torch.equal(dx, dx2)
+    sp = case[1]
+    for name, off, n in zip(sp.names, sp.offsets, sp.numels):
+        if bgrad or name != "ffn1_bias":
+            assert torch.equal(g[off:off + n], g2[off:off + n]), name
+
+
+def test_block_backward_grouped_beside_non_flat_biases(cuda, monkeypatch):
+    """The QKV and FFN1 biases outside the flat space: their gradients come from the column-sum
+    kernels (returned to autograd) while the weight pairs beside them still go out grouped,
+    without a bias in the GEMM."""
+    leave_out = ("qkv_bias", "ffn1_bias")
+    case = _grouped_block_case(cuda, leave_out)
+    y_ref, dx_ref, g_ref, loose_ref = case[-1]
+    y, dx, g, loose, groups, native = _run_grouped_block(case, monkeypatch, False, None, True)
+    assert groups == [(_FFN_PAIR, (False, False)), (_ATTN_PAIR, (False, False))]
+    assert native == [True, True]
+    assert _rel(y, y_ref) < 1e-2
+    assert _rel(dx, dx_ref) < 2e-2
+    assert _rel(g, g_ref) < 2e-2
+    for got, ref_ in zip(loose, loose_ref):
+        assert _rel(got, ref_) < 2e-2
+
+
 @pytest.mark.parametrize("name", ["adamw", "lamb"])
 def test_optimizer_step_scalars_under_cpu_run_ahead(cuda, name):
     """The CPU queues several optimizer steps behind a long GPU kernel without synchronising:
