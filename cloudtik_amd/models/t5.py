@@ -1,7 +1,8 @@
 """T5 encoder-decoder (t5-small / base / large topologies).
 
 Reference workload: the quickstart T5 inference (applications/ai/quickstart, HF
-``T5ForConditionalGeneration``).  Random-init weights, same architecture:
+``T5ForConditionalGeneration``).  Random-init weights or a local HF
+checkpoint (``from_hf_config`` / ``load_hf_state_dict``), same architecture:
 pre-norm blocks with RMS LayerNorm (no mean, no bias), un-scaled attention with a learned
 bucketed relative-position bias shared by all layers of a stack, ReLU (v1.0) or gated-GELU
 (v1.1) feed-forward, tied input/output embeddings scaled by d_model^-0.5.
@@ -12,7 +13,8 @@ key - query) and added inside the MFMA flash-attention kernel (``ops.attention_r
 so inference never materialises an [H, Sq, Sk] bias; cross-attention uses the MFMA kernel
 with the per-key padding mask; training self-attention (which needs the bias gradient) uses
 SDPA with the gathered bias; the training loss is the fused linear + cross-entropy HIP
-kernel over the 32128-token vocabulary; generation keeps a per-layer KV cache.
+kernel over the 32128-token vocabulary; generation keeps a per-layer KV cache and replays
+the decode step as a HIP graph, greedy or with beam search (``ops/beam.py``, ``csrc/beam.hip``).
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from cloudtik_amd import ops
+from cloudtik_amd.ops import beam as beam_ops
 
 logger = logging.getLogger(__name__)
 
@@ -282,14 +285,35 @@ class T5ForConditionalGeneration(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 32,
-                 use_graph: Optional[bool] = None) -> torch.Tensor:
+                 use_graph: Optional[bool] = None, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping: bool = False, return_scores: bool = False, trace: Optional[list] = None):
         """Greedy decoding with a KV cache (self-attention K/V grow; cross K/V computed once).
 
         On the GPU the decode step is captured once into a HIP graph over a static KV cache
         of ``max_new_tokens`` slots and replayed per token (``_generate_graph``): a decode step
-        is ~15 small kernels per layer, so launch overhead, not math, bounds eager decoding."""
+        is ~15 small kernels per layer, so launch overhead, not math, bounds eager decoding.
+
+        ``num_beams`` > 1 searches with that many beams (``ops.beam`` states the rules: the
+        tensor-only beam search of HF ``generate``, every step run) and returns the best
+        finished hypothesis [B, max_new_tokens], pad after EOS; with ``return_scores`` also its
+        score, sum of log-probabilities / length**``length_penalty``, fp32 [B].  On the GPU the
+        step runs at batch B * num_beams inside the same kind of graph, with the bookkeeping
+        in the beam kernels (``_generate_beam_static``); ``use_graph=False``, a ``trace`` list and
+        the CPU run the eager reference loop, which appends every step's 2K candidate scores
+        [B, 2K] to ``trace``."""
         if use_graph is None:
             use_graph = input_ids.is_cuda and os.environ.get("CLOUDTIK_AMD_T5_GRAPH", "1") == "1"
+        beam_ops.check_beam_args(num_beams, self.cfg.vocab_size, early_stopping)
+        if num_beams > 1:
+            if use_graph and input_ids.is_cuda and trace is None:
+                seq, score = self._generate_beam_static(input_ids, attention_mask, max_new_tokens, num_beams,
+                                                        length_penalty, early_stopping)
+            else:
+                seq, score = self._generate_beam_eager(input_ids, attention_mask, max_new_tokens, num_beams,
+                                                       length_penalty, early_stopping, trace)
+            return (seq, score) if return_scores else seq
+        if return_scores or trace is not None:
+            raise ValueError("return_scores and trace belong to beam search (num_beams > 1)")
         if use_graph and input_ids.is_cuda:
             try:
                 return self._generate_graph(input_ids, attention_mask, max_new_tokens)
@@ -335,6 +359,34 @@ class T5ForConditionalGeneration(nn.Module):
             st["graph"].replay()
         return st["out"].clone()
 
+    def _decode_step_static(self, cur, pos, slots, kc, vc, cross, enc_bias):
+        """One decoder step over static buffers, free of host decisions (capturable): embeds
+        ``cur`` [B, 1], writes each layer's self-attention K/V into slot ``pos`` of ``kc`` / ``vc``
+        [B, T, H, D] and returns the final hidden states [B, 1, d_model]."""
+        cfg, dec = self.cfg, self.decoder
+        B, T = cur.shape[0], slots.shape[0]
+        x = dec.embed(cur)
+        bucket = relative_position_bucket(slots - pos, False, cfg.relative_attention_num_buckets,
+                                          cfg.relative_attention_max_distance)
+        relvec = dec.blocks[0].sa.rel(bucket).t().float().contiguous()     # query at `pos`, keys 0..T-1
+        key_bias = torch.where(slots <= pos, 0.0, -1e9).float()[None].expand(B, T).contiguous()
+        for i, blk in enumerate(dec.blocks):
+            h = blk.ln_sa(x)
+            a = blk.sa
+            q, k, v = a._split(a.q(h)), a._split(a.k(h)), a._split(a.v(h))
+            kc[i].index_copy_(1, pos, k)
+            vc[i].index_copy_(1, pos, v)
+            o = ops.attention_relbias(q, kc[i], vc[i], relvec, 0, key_bias, scale=1.0, causal=False)
+            x = x + a.o(o.reshape(B, 1, -1))
+            h = blk.ln_ca(x)
+            c = blk.ca
+            q = c._split(c.q(h))
+            o = ops.attention(q.transpose(1, 2), cross[i][0].transpose(1, 2), cross[i][1].transpose(1, 2),
+                              key_bias=enc_bias, scale=1.0).transpose(1, 2)
+            x = x + c.o(o.reshape(B, 1, -1))
+            x = x + blk.ff(blk.ln_ff(x))
+        return dec.final(x)
+
     def _capture_decode(self, B, S, T, dtype, dev, masked: bool):
         cfg = self.cfg
         H, D = cfg.num_heads, cfg.d_kv
@@ -350,30 +402,9 @@ class T5ForConditionalGeneration(nn.Module):
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         slots = torch.arange(T, device=dev)
         pad = torch.full((B,), cfg.pad_token_id, dtype=torch.long, device=dev)
-        sa0 = dec.blocks[0].sa
 
         def step():
-            x = dec.embed(cur)
-            bucket = relative_position_bucket(slots - pos, False, cfg.relative_attention_num_buckets,
-                                              cfg.relative_attention_max_distance)
-            relvec = sa0.rel(bucket).t().float().contiguous()              # query at `pos`, keys 0..T-1
-            key_bias = torch.where(slots <= pos, 0.0, -1e9).float()[None].expand(B, T).contiguous()
-            for i, blk in enumerate(dec.blocks):
-                h = blk.ln_sa(x)
-                a = blk.sa
-                q, k, v = a._split(a.q(h)), a._split(a.k(h)), a._split(a.v(h))
-                kc[i].index_copy_(1, pos, k)
-                vc[i].index_copy_(1, pos, v)
-                o = ops.attention_relbias(q, kc[i], vc[i], relvec, 0, key_bias, scale=1.0, causal=False)
-                x = x + a.o(o.reshape(B, 1, -1))
-                h = blk.ln_ca(x)
-                c = blk.ca
-                q = c._split(c.q(h))
-                o = ops.attention(q.transpose(1, 2), cross[i][0].transpose(1, 2), cross[i][1].transpose(1, 2),
-                                  key_bias=enc_bias, scale=1.0).transpose(1, 2)
-                x = x + c.o(o.reshape(B, 1, -1))
-                x = x + blk.ff(blk.ln_ff(x))
-            x = dec.final(x)
+            x = self._decode_step_static(cur, pos, slots, kc, vc, cross, enc_bias)
             nxt = self.logits(x[:, -1]).float().argmax(-1)
             nxt = torch.where(done, pad, nxt)
             out.index_copy_(1, pos, nxt[:, None])
@@ -396,4 +427,228 @@ class T5ForConditionalGeneration(nn.Module):
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             step()
-        return {"graph": graph, "cross": cross, "enc_bias": enc_bias, "out": out, "reset": reset}
+        # "step" keeps the buffers only the captured kernels still use (the caches) allocated
+        return {"graph": graph, "cross": cross, "enc_bias": enc_bias, "out": out, "reset": reset, "step": step}
+
+    # ------------------------------------------------------------------------- beam search
+    @torch.no_grad()
+    def _generate_beam_eager(self, input_ids, attention_mask, max_new, K, length_penalty, early_stopping, trace=None):
+        """The reference beam loop, any device and dtype: the growing-cache decoder at batch
+        B * K and ``beam_step_reference`` / ``cache_reorder_reference`` after every step."""
+        cfg, dev = self.cfg, input_ids.device
+        B, T = input_ids.shape[0], max_new
+        enc, _ = self.encoder(input_ids, attention_mask)
+        enc = enc.repeat_interleave(K, 0)
+        mask = attention_mask.repeat_interleave(K, 0) if attention_mask is not None else None
+        state = beam_ops.new_state(B, K, T, cfg.pad_token_id, dev)
+        len_pen = beam_ops.length_penalty_table(T, length_penalty, dev)
+        cur = torch.full((B * K, 1), cfg.decoder_start_token_id, dtype=torch.long, device=dev)
+        caches = None
+        for t in range(T):
+            dec, caches = self.decoder(cur, enc=enc, enc_mask=mask, caches=caches, offset=t)
+            state, beam_idx, nxt, cand, _ = beam_ops.beam_step_reference(
+                self.logits(dec[:, -1]), state, t, len_pen, cfg.eos_token_id, early_stopping)
+            if trace is not None:
+                trace.append(cand)
+            for c in caches:                       # cross K/V are the same for every beam of an item
+                c["self"] = tuple(beam_ops.cache_reorder_reference(c["self"], beam_idx))
+            cur = nxt[:, None]
+        return state["fin_seq"][:, 0].clone(), state["fin_score"][:, 0].clone()
+
+    @torch.no_grad()
+    def _generate_beam_static(self, input_ids, attention_mask, max_new, K, length_penalty=1.0, early_stopping=False,
+                              fused: bool = True, graph: bool = True, trace=None, select: str = "sort"):
+        """Beam search over the static-cache decode step at batch B * K.  ``fused``: the beam
+        kernels do the bookkeeping (else the PyTorch reference does, on the same step, so both
+        see the same logits); ``graph``: two captured graphs, one per cache parity, are replayed
+        in turn (else the same step runs eagerly and fills ``trace``).  Captures are cached like
+        the greedy ones, additionally by (K, length_penalty, early_stopping)."""
+        dev = input_ids.device
+        B, S, T = input_ids.shape[0], input_ids.shape[1], max_new
+        if trace is not None and graph:
+            raise ValueError("trace needs graph=False")
+        enc, _ = self.encoder(input_ids, attention_mask)
+        masked = attention_mask is not None
+        key = ("beam", B, S, T, masked, str(dev), K, float(length_penalty), bool(early_stopping), fused, graph, select)
+        cache = getattr(self, "_graphs", None)
+        if cache is None:
+            cache = self._graphs = {}
+        st = cache.get(key)
+        if st is None:
+            st = cache[key] = self._capture_beam_decode(B, S, T, enc.dtype, dev, masked, K, length_penalty,
+                                                        early_stopping, fused, graph, select)
+        for i, b in enumerate(self.decoder.blocks):     # cross K/V: expanded to B * K rows once per call
+            st["cross"][i][0].copy_(b.ca._split(b.ca.k(enc)).repeat_interleave(K, 0))
+            st["cross"][i][1].copy_(b.ca._split(b.ca.v(enc)).repeat_interleave(K, 0))
+        if masked:
+            st["enc_bias"].copy_(((1.0 - attention_mask.float()) * -1e9).repeat_interleave(K, 0))
+        st["reset"]()
+        st["trace"][0] = trace
+        for t in range(T):
+            st["steps"][t & 1]()
+        st["trace"][0] = None
+        state = st["state"]
+        return state["fin_seq"][:, 0].clone(), state["fin_score"][:, 0].clone()
+
+    def _capture_beam_decode(self, B, S, T, dtype, dev, masked, K, length_penalty, early_stopping, fused, graph,
+                             select):
+        cfg = self.cfg
+        H, D, R = cfg.num_heads, cfg.d_kv, B * K
+        n = len(self.decoder.blocks)
+
+        def zeros(*shape):
+            return torch.zeros(*shape, dtype=dtype, device=dev)
+
+        # self-attention caches in two sets: step t reads and extends set t & 1, and the reorder
+        # gathers its rows by source beam into the other set, which step t + 1 uses
+        kc = [[zeros(R, T, H, D) for _ in range(n)] for _ in range(2)]
+        vc = [[zeros(R, T, H, D) for _ in range(n)] for _ in range(2)]
+        cross = [(zeros(R, S, H, D), zeros(R, S, H, D)) for _ in range(n)]
+        enc_bias = torch.zeros(R, S, device=dev) if masked else None
+        cur = torch.full((R, 1), cfg.decoder_start_token_id, dtype=torch.long, device=dev)
+        pos = torch.zeros(1, dtype=torch.long, device=dev)
+        arrive = torch.zeros(1, dtype=torch.int32, device=dev)
+        beam_idx = torch.zeros(R, dtype=torch.long, device=dev)
+        slots = torch.arange(T, device=dev)
+        state = beam_ops.new_state(B, K, T, cfg.pad_token_id, dev)
+        len_pen = beam_ops.length_penalty_table(T, length_penalty, dev)
+        reorder = [beam_ops.CacheReorder(kc[p] + vc[p], kc[1 - p] + vc[1 - p]) for p in range(2)] if fused else None
+        trace = [None]
+
+        def step(p):
+            x = self._decode_step_static(cur, pos, slots, kc[p], vc[p], cross, enc_bias)
+            logits = self.logits(x[:, -1])
+            if fused:
+                beam_ops.beam_step(logits, state, pos, arrive, len_pen, beam_idx, cur, cfg.eos_token_id, early_stopping)
+                reorder[p](beam_idx, pos)
+                return
+            new, src, nxt, cand, _ = beam_ops.beam_step_reference(logits, state, pos, len_pen, cfg.eos_token_id,
+                                                                  early_stopping, select=select)
+            if trace[0] is not None:
+                trace[0].append(cand)
+            for name, v in new.items():
+                state[name].copy_(v)
+            cur.copy_(nxt[:, None])
+            beam_ops.cache_reorder_reference(kc[p] + vc[p], src, out=kc[1 - p] + vc[1 - p])
+            pos.add_(1)
+
+        def reset():
+            cur.fill_(cfg.decoder_start_token_id)
+            pos.zero_()
+            arrive.zero_()
+            beam_ops.reset_state(state, cfg.pad_token_id)
+
+        steps = [lambda: step(0), lambda: step(1)]
+        if graph:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):      # warm up (lazy inits, library handles) off the capture
+                for p in range(2):
+                    reset()
+                    step(p)
+            torch.cuda.current_stream().wait_stream(side)
+            reset()
+            graphs = [torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()]
+            for p in range(2):
+                with torch.cuda.graph(graphs[p]):
+                    step(p)
+            steps = [graphs[0].replay, graphs[1].replay]
+        # "step" keeps what only the captured kernels still use (caches, pointer tables) allocated
+        return {"steps": steps, "cross": cross, "enc_bias": enc_bias, "state": state, "reset": reset, "trace": trace,
+                "step": step}
+
+    # --------------------------------------------------------------------- pretrained weights
+    @classmethod
+    def from_hf_config(cls, config, device=None, dtype=torch.bfloat16):
+        """A model with the topology of a HF T5 config: a ``T5Config`` of the library, a dict, or
+        the path of a local ``config.json``."""
+        if isinstance(config, (str, os.PathLike)):
+            import json
+            with open(config) as f:
+                config = json.load(f)
+        elif not isinstance(config, dict):
+            config = config.to_dict()
+        def get(name, default):                    # a key saved as null counts as absent
+            v = config.get(name)
+            return default if v is None else v
+
+        act = get("feed_forward_proj", "relu")
+        if act not in ("relu", "gated-gelu"):
+            raise ValueError(f"unsupported feed_forward_proj {act!r} (relu and gated-gelu are)")
+        if not get("tie_word_embeddings", True):
+            raise ValueError("checkpoints with an untied output head (tie_word_embeddings=False) are not supported")
+        eos = get("eos_token_id", 1)
+        if isinstance(eos, (list, tuple)):
+            if len(eos) != 1:
+                raise ValueError(f"one eos_token_id is supported, got {eos}")
+            eos = eos[0]
+        cfg = T5Config(
+            vocab_size=config["vocab_size"], d_model=config["d_model"], d_kv=config["d_kv"], d_ff=config["d_ff"],
+            num_layers=config["num_layers"], num_decoder_layers=get("num_decoder_layers", config["num_layers"]),
+            num_heads=config["num_heads"],
+            relative_attention_num_buckets=get("relative_attention_num_buckets", 32),
+            relative_attention_max_distance=get("relative_attention_max_distance", 128),
+            dropout_rate=get("dropout_rate", 0.1), layer_norm_epsilon=get("layer_norm_epsilon", 1e-6),
+            gated_gelu=act == "gated-gelu", pad_token_id=get("pad_token_id", 0),
+            decoder_start_token_id=get("decoder_start_token_id", 0), eos_token_id=eos)
+        return cls(cfg, device=device, dtype=dtype)
+
+    def _hf_name_map(self):
+        """{our parameter name: HF state-dict key}."""
+        names = {"shared.weight": "shared.weight"}
+        for stack, blocks in (("encoder", self.encoder.blocks), ("decoder", self.decoder.blocks)):
+            names[f"{stack}.final.weight"] = f"{stack}.final_layer_norm.weight"
+            ff = 2 if stack == "decoder" else 1
+            for i, _ in enumerate(blocks):
+                ours, hf = f"{stack}.blocks.{i}", f"{stack}.block.{i}.layer"
+                for w in "qkvo":
+                    names[f"{ours}.sa.{w}.weight"] = f"{hf}.0.SelfAttention.{w}.weight"
+                if i == 0:
+                    names[f"{ours}.sa.rel.weight"] = f"{hf}.0.SelfAttention.relative_attention_bias.weight"
+                names[f"{ours}.ln_sa.weight"] = f"{hf}.0.layer_norm.weight"
+                if stack == "decoder":
+                    for w in "qkvo":
+                        names[f"{ours}.ca.{w}.weight"] = f"{hf}.1.EncDecAttention.{w}.weight"
+                    names[f"{ours}.ln_ca.weight"] = f"{hf}.1.layer_norm.weight"
+                names[f"{ours}.ln_ff.weight"] = f"{hf}.{ff}.layer_norm.weight"
+                if self.cfg.gated_gelu:
+                    names[f"{ours}.ff.wi.weight"] = f"{hf}.{ff}.DenseReluDense.wi_0.weight"
+                    names[f"{ours}.ff.wi_1.weight"] = f"{hf}.{ff}.DenseReluDense.wi_1.weight"
+                else:
+                    names[f"{ours}.ff.wi.weight"] = f"{hf}.{ff}.DenseReluDense.wi.weight"
+                names[f"{ours}.ff.wo.weight"] = f"{hf}.{ff}.DenseReluDense.wo.weight"
+        return names
+
+    @torch.no_grad()
+    def load_hf_state_dict(self, state_dict):
+        """Copy the weights of a HF ``T5ForConditionalGeneration`` state dict (a dict, or the path
+        of a local ``.bin`` / ``.pt`` / ``.safetensors`` file) into this model, cast to its dtype.
+        Every parameter must be present with its shape, and no key may be left over: the tied
+        copies of the embedding are accepted when they equal it, an untied ``lm_head`` is not."""
+        if isinstance(state_dict, (str, os.PathLike)):
+            path = os.fspath(state_dict)
+            if path.endswith(".safetensors"):
+                from safetensors.torch import load_file
+                state_dict = load_file(path)
+            else:
+                state_dict = torch.load(path, map_location="cpu", weights_only=True)
+        sd = dict(state_dict)
+        shared = sd.get("shared.weight")
+        for tied in ("encoder.embed_tokens.weight", "decoder.embed_tokens.weight", "lm_head.weight"):
+            w = sd.pop(tied, None)
+            if w is not None and (shared is None or w.shape != shared.shape or not torch.equal(w, shared.to(w.device))):
+                raise ValueError(f"{tied} differs from shared.weight: untied embeddings / output heads are not supported")
+        params = dict(self.named_parameters())
+        names = self._hf_name_map()
+        assert set(names) == set(params), sorted(set(names) ^ set(params))
+        missing = sorted(hf for hf in names.values() if hf not in sd)
+        extra = sorted(set(sd) - set(names.values()))
+        if missing or extra:
+            raise KeyError(f"load_hf_state_dict: missing keys {missing}, unknown keys {extra}")
+        for ours, hf in names.items():
+            if params[ours].shape != sd[hf].shape:
+                raise ValueError(f"load_hf_state_dict: {hf} has shape {tuple(sd[hf].shape)}, "
+                                 f"expected {tuple(params[ours].shape)}")
+        for ours, hf in names.items():
+            params[ours].copy_(sd[hf])
+        return self                 # in place: graphs captured earlier read the new weights

@@ -130,3 +130,5 @@ from .deform import (DeformConv, DeformRoIPooling, DeformRoIPoolingPack, Modulat
 from .rnnt import rnnt_loss, rnnt_loss_reference  # noqa: E402,F401
 from .quant import (layer_norm_quant, linear_i8, linear_i8_static, quantize_rows, quantize_static,  # noqa: E402,F401
                     quantize_weight)
+from . import beam  # noqa: E402,F401
+from .beam import beam_step, beam_step_reference, beam_topk, cache_reorder_reference  # noqa: E402,F401

@@ -848,6 +848,7 @@ void register_p2p(pybind11::module& m);    // bindings_p2p.cpp
 void register_lt(pybind11::module& m);     // bindings_lt.cpp
 void register_conv(pybind11::module& m);   // bindings_conv.cpp
 void register_quant(pybind11::module& m);  // bindings_quant.cpp
+void register_beam(pybind11::module& m);   // bindings_beam.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "cloudtik_amd CDNA4 (gfx950) op library";
@@ -858,6 +859,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_lt(m);
   register_conv(m);
   register_quant(m);
+  register_beam(m);
   m.def("maxpool3s2_bwd_bn", &maxpool3s2_bwd_bn);
   m.def("bn_fwd_train_given2", &bn_fwd_train_given2);
   m.def("bn_bwd_given_pair", &bn_bwd_given_pair);
