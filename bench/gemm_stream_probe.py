@@ -1,12 +1,13 @@
 """Streamed persistent MFMA GEMM (csrc/gemm_nt.hip gemm_nt_stream_kernel) vs the one-tile kernel
-vs hipBLASLt on the BERT-large forward (+ bias) and data-gradient GEMMs, tokens 32768.
+vs hipBLASLt on the BERT-large forward (+ bias) and data-gradient GEMMs, tokens 32768, and the
+two fused FFN sites (EPI 6 forward, EPI 7 data gradient: one-tile vs streamed only).
 
 Correctness first (relative error vs an fp32 reference on the same random operands), then
 timing in interleaved rounds within one process (HIP events over ``--iters`` back-to-back
 calls per round; the median and min over ``--rounds`` rounds are reported, cdna_hip_programming
 §5.4 rule 24).  Prints one JSON line per shape and a markdown table on stderr.
 
-    python bench/gemm_stream_probe.py [--tokens 32768] [--rounds 5] [--iters 20]
+    python bench/gemm_stream_probe.py [--tokens 32768] [--rounds 5] [--iters 20] [--only case,case]
 """
 import argparse
 import json
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--wgs", type=int, default=0, help="persistent workgroups (0: one per CU)")
+    ap.add_argument("--only", default="", help="comma list of case names (default: all)")
     a = ap.parse_args()
     from cloudtik_amd import ops
     C = ops.require_native()
@@ -50,11 +52,35 @@ def main():
     cases = [("qkv_fwd", "fwd", T, 3072, 1024), ("wo_fwd", "fwd", T, 1024, 1024), ("ffn2_fwd", "fwd", T, 1024, 4096),
              ("ffn1_fwd_plain", "fwd", T, 4096, 1024),
              ("qkv_dgrad_dx", "dgrad", T, 1024, 3072), ("wo_dgrad_dx", "dgrad", T, 1024, 1024),
-             ("ffn1_dgrad_dx", "dgrad", T, 1024, 4096), ("ffn2_dgrad_dh", "dgrad", T, 4096, 1024)]
+             ("ffn1_dgrad_dx", "dgrad", T, 1024, 4096), ("ffn2_dgrad_dh", "dgrad", T, 4096, 1024),
+             # the two fused FFN sites: EPI 6 (bias + GELU, stores h and gelu') and EPI 7 (x gelu');
+             # no hipBLASLt column (it has neither epilogue), one-tile against streamed
+             ("ffn1_fwd_epi6", "epi6", T, 4096, 1024), ("ffn_dgrad_epi7", "epi7", T, 4096, 1024)]
+    if a.only:
+        cases = [c for c in cases if c[0] in a.only.split(",")]
     rows = []
     for name, kind, M, N, K in cases:
         A = rnd(M, K)
-        if kind == "fwd":
+        if kind == "epi6":
+            W = rnd(N, K, sc=K ** -0.5)
+            b = rnd(N, sc=0.1)
+            z = A.float() @ W.float().t() + b.float()
+            ref = 0.5 * z * (1 + torch.erf(z * 0.5 ** 0.5))
+            del z
+            aux = torch.empty(M, N, device="cuda", dtype=bf)
+            fns = {"one_tile": lambda D=torch.empty(M, N, device="cuda", dtype=bf): (C.gemm_nt(A, W, D, 6, False, b, aux,
+                                                                                                None), D)[1],
+                   "stream": lambda D=torch.empty(M, N, device="cuda", dtype=bf): (C.gemm_nt_stream(
+                       A, W, D, b, False, a.wgs, False, epi=6, aux=aux), D)[1]}
+        elif kind == "epi7":
+            W = rnd(K, N, sc=K ** -0.5)
+            aux = rnd(M, N)
+            ref = (A.float() @ W.float()) * aux.float()
+            fns = {"one_tile": lambda D=torch.empty(M, N, device="cuda", dtype=bf): (C.gemm_nn(A, W, D, 7, False, None,
+                                                                                                aux, None), D)[1],
+                   "stream": lambda D=torch.empty(M, N, device="cuda", dtype=bf): (C.gemm_nt_stream(
+                       A, W, D, None, True, a.wgs, False, epi=7, aux=aux), D)[1]}
+        elif kind == "fwd":
             W = rnd(N, K, sc=K ** -0.5)
             b = rnd(N, sc=0.1)
             ref = (A.float() @ W.float().t() + b.float())
@@ -99,8 +125,10 @@ def main():
           file=sys.stderr)
     print("|---|---|---:|---:|---:|---:|---:|", file=sys.stderr)
     for r in rows:
-        print(f"| {r['case']} | {r['M']}x{r['N']}x{r['K']} | {r['hipblaslt_us']} | {r['one_tile_us']} | "
-              f"{r['stream_us']} | {r['stream_tflops']} | {r['hipblaslt_us'] / r['stream_us']:.3f}x |", file=sys.stderr)
+        lt = r.get("hipblaslt_us")
+        vs = f"{lt / r['stream_us']:.3f}x" if lt else "-"
+        print(f"| {r['case']} | {r['M']}x{r['N']}x{r['K']} | {lt if lt else '-'} | {r['one_tile_us']} | "
+              f"{r['stream_us']} | {r['stream_tflops']} | {vs} |", file=sys.stderr)
 
 
 if __name__ == "__main__":

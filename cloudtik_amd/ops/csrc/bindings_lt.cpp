@@ -331,12 +331,14 @@ bool gemm_nn(at::Tensor A, at::Tensor B, at::Tensor D, int64_t epi, bool accumul
 }
 
 extern "C" int ct_gemm_nt_stream(const void*, long, const void*, long, void*, long, int, int, int, int, const void*,
-                                 int, int, int, hipStream_t);
+                                 int, int, int, void*, long, hipStream_t);
 
 // Streamed persistent MFMA GEMM (one workgroup per CU walks its output tiles with one
 // continuous K-tile DMA stream): D = A @ B^T (b_kn: B stored [K, N], D = A @ B) [+ bias[N]].
+// epi < 0: plain, or + bias when one is given; 6 (NT): D = gelu(. + bias), aux = gelu'(. + bias);
+// 7 (NN): D = . * aux.  False (nothing launched) for a combination the kernel does not have.
 bool gemm_nt_stream(at::Tensor A, at::Tensor B, at::Tensor D, c10::optional<at::Tensor> bias, bool b_kn,
-                    int64_t wgs, bool accumulate) {
+                    int64_t wgs, bool accumulate, int64_t epi, c10::optional<at::Tensor> aux) {
   TORCH_CHECK(A.is_cuda() && B.is_cuda() && D.is_cuda(), "gemm_nt_stream: GPU tensors");
   TORCH_CHECK(A.scalar_type() == at::kBFloat16 && B.scalar_type() == at::kBFloat16 &&
               D.scalar_type() == at::kBFloat16, "gemm_nt_stream: bf16 operands");
@@ -344,12 +346,16 @@ bool gemm_nt_stream(at::Tensor A, at::Tensor B, at::Tensor D, c10::optional<at::
   const long M = A.size(0), K = A.size(1), N = b_kn ? B.size(1) : B.size(0);
   TORCH_CHECK((b_kn ? B.size(0) : B.size(1)) == K && D.size(0) == M && D.size(1) == N,
               "gemm_nt_stream: shape mismatch");
-  const bool hb = bias.has_value() && bias->defined();
+  const bool hb = bias.has_value() && bias->defined(), ha = aux.has_value() && aux->defined();
   if (hb) TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N,
                       "gemm_nt_stream: bias");
+  if (ha) TORCH_CHECK(aux->is_cuda() && aux->scalar_type() == at::kBFloat16 && rowmajor_ok(*aux) &&
+                      aux->size(0) == M && aux->size(1) == N, "gemm_nt_stream: aux");
+  if (epi < 0) epi = hb ? 5 : 0;
   int rc = ct_gemm_nt_stream(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), D.data_ptr(), D.stride(0),
-                             (int)M, (int)N, (int)K, hb ? 5 : 0, hb ? bias->data_ptr() : nullptr, b_kn ? 1 : 0,
-                             (int)wgs, accumulate ? 1 : 0, at::hip::getCurrentHIPStream().stream());
+                             (int)M, (int)N, (int)K, (int)epi, hb ? bias->data_ptr() : nullptr, b_kn ? 1 : 0,
+                             (int)wgs, accumulate ? 1 : 0, ha ? aux->data_ptr() : nullptr,
+                             ha ? aux->stride(0) : 0, at::hip::getCurrentHIPStream().stream());
   return rc == 0;
 }
 
@@ -492,7 +498,8 @@ void register_lt(pybind11::module& m) {
   m.def("gemm_nt", &gemm_nt, "hand-written MFMA GEMM A @ B^T with fused epilogues");
   m.def("gemm_nt_stream", &gemm_nt_stream, "streamed persistent MFMA GEMM A @ B^T / A @ B (+ bias)",
         pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("D"), pybind11::arg("bias") = pybind11::none(), pybind11::arg("b_kn") = false,
-        pybind11::arg("wgs") = 0, pybind11::arg("accumulate") = false);
+        pybind11::arg("wgs") = 0, pybind11::arg("accumulate") = false, pybind11::arg("epi") = -1,
+        pybind11::arg("aux") = pybind11::none());
   m.def("gemm_pp", &gemm_pp, "paired-tile persistent MFMA GEMM A @ B^T (epilogue of one tile beside another's K loop)",
         pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("D"), pybind11::arg("epi") = 0,
         pybind11::arg("bias") = pybind11::none(), pybind11::arg("aux") = pybind11::none(), pybind11::arg("wgs") = 0,

@@ -285,11 +285,15 @@ __device__ __forceinline__ nt_s16x8 nt_fragment(const char* img, int r0, int ks,
 // state (the half of 4 phases ago has landed).  Measured alternatives that change nothing
 // (within 2 %): two halves in each of the read-light phases q1 / q3 only, and DMA issued
 // before instead of after the phase's fragment reads.
-template <int POS>
+// POS 3 (streamed kernel only): the first K-tile after an output-tile boundary, whose waits
+// step over the E vector-memory instructions of the finished tile's epilogue (NtStreamE).
+template <int POS, int E = 0>
 struct NtPlan {
-  static constexpr bool issue(int q) { return POS == 0 || (POS == 1 && q < 2); }
+  static_assert(POS == 3 ? (E >= 0 && 8 + E <= 63) : E == 0, "vmcnt is a 6-bit field");
+  static constexpr bool issue(int q) { return POS == 0 || POS == 3 || (POS == 1 && q < 2); }
   static constexpr int wait(int q) {
-    return POS == 0 ? 8 : (POS == 1 ? (q < 2 ? 8 : (q == 2 ? 6 : 4)) : (q == 0 ? 2 : 0));
+    return POS == 3 ? 8 + E
+                    : (POS == 0 ? 8 : (POS == 1 ? (q < 2 ? 8 : (q == 2 ? 6 : 4)) : (q == 0 ? 2 : 0)));
   }
 };
 
@@ -779,11 +783,47 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_kernel(NtGroupArgs g) {
 // output tile are issued by the last phases of the current one exactly as within a tile, so
 // the next tile's operands land while this tile's epilogue stores run (the epilogue of one
 // wave group also overlaps the other group's MFMA phase: the groups run one barrier apart).
-// Nothing else changes: same phases, same LDS images and swizzles, same counted vmcnt waits
-// (epilogue stores / bias loads are younger than the in-flight DMAs, so "all but the N youngest
-// vector-memory ops" only ever waits for MORE than the pipeline needs).  The one-tile kernel
+// Nothing else changes: same phases, same LDS images and swizzles, same K order, MFMA order
+// and epilogue code (results are bit-equal to the one-tile kernel's).  The one-tile kernel
 // pays a workgroup launch, a cold prologue (first DMA latency) and an idle epilogue per tile:
 // at K = 1024 (16 K-tiles) that is a large share of the tile.
+//
+// Counted waits across a tile boundary.  Stores count in vmcnt like loads and retire in issue
+// order, and the epilogue's stores (and the next tile's bias loads) are issued AFTER the four
+// half-tile DMAs in flight at the end of a tile and BEFORE the DMAs of the next tile's first
+// K-tile.  With h-4 .. h-1 those four halves, E the epilogue's instructions and h0 .. h3 the
+// halves of the first K-tile, phase q of that K-tile needs half h(q-4), and what is younger
+// than it is (3 - q) older halves, the E instructions and the (q + 1) halves issued so far:
+// 4 halves of 2 DMAs each + E = 8 + E instructions, so the four phases wait vmcnt(8 + E)
+// (NtPlan<3, E>).  A plain vmcnt(8) there is correct but waits for all but the
+// last 8 - 2(q + 1) stores to be acknowledged, with the matrix cores idle.  From the second
+// K-tile on the needed half is younger than the stores and the plan is the steady one.  A
+// count too small only waits longer; one too large would read LDS before the DMA has landed,
+// so the plan is used only where the E instructions are certainly there: not on a tile that
+// begins inside the stream's drain (NtPlan<1> / <2> keep their waits) and not when a tile is
+// a single K-tile.  The kernel's very first K-tile uses it too (no branch between K-tile
+// variants in the loop): the prologue there waits for everything it issued, so all four
+// halves the K-tile's phases need have landed whatever the count.
+//
+// E per epilogue (instructions per wave between the last DMA of a tile and the first DMA of
+// the next; counted in the disassembly too, profiles/ffn_stream/SUMMARY.md).  nt_epilogue
+// stores 8 row blocks x NJ / 2 = 2 column pairs = 16 dwordx4 per output tensor; EPI 6 writes
+// two tensors (h and gelu').  nt_preload_bias loads NJ = 4 8-byte pieces (the next tile's,
+// issued just before the stores: finish_tile).  vmcnt(N) says "everything but the N youngest
+// ISSUED instructions is complete", whether or not some of those N have completed too, so E
+// may count any instruction that is certainly issued there and none that may not be.  The
+// loads the epilogue consumes itself (EPI 7's aux, the old D when accumulating -- a runtime
+// choice) are left out: they come before the stores and are waited for by the epilogue's own
+// arithmetic, which retires the older DMAs with them, so leaving them out costs nothing.
+template <int EPI>
+struct NtStreamE {
+  static constexpr int stores = EPI == NT_EPI_BIAS_GELU_DAUX ? 32 : 16;
+  // the launcher refuses a null bias for these two, so the 4 loads are always issued
+  static constexpr int bias_loads = (EPI == NT_EPI_BIAS || EPI == NT_EPI_BIAS_GELU_DAUX) ? 4 : 0;
+  static constexpr int value = stores + bias_loads;
+  static_assert(EPI == NT_EPI_PLAIN || EPI == NT_EPI_BIAS || EPI == NT_EPI_BIAS_GELU_DAUX ||
+                EPI == NT_EPI_MUL_AUX_BGRAD, "streamed kernel: epilogues 0, 5, 6, 7");
+};
 struct NtStream {
   int nk;            // K-tiles per output tile
   int total_k;       // K-tiles of this workgroup's whole stream
@@ -861,14 +901,14 @@ __device__ __forceinline__ void nt_stage_kt(const NtCtx& c, const NtSOff& so, co
 // one K-tile of the stream: phases 0 / 1 stage B1 / A1 of K-tile t + 1 (cursor q1), phases 2 / 3
 // A0 / B0 of K-tile t + 2 (cursor q2) -- the one-tile kernel's half order (nt_stage_v), with
 // every slot a compile-time constant
-template <int POS, int LAY>
+template <int POS, int LAY, int E = 0>
 __device__ __forceinline__ void nt_ktile_stream(const NtCtx& c, const NtSOff& so, const NtKCur& q1,
                                                 const NtKCur& q2, int t, f32x4 (&acc)[8][4],
                                                 nt_s16x8 (&fa)[2][4][2], nt_s16x8 (&fb)[2][2][2]) {
   const char* buf = c.lds + (t & 1) * NT_BUF;
   char* nbuf = c.lds + ((t + 1) & 1) * NT_BUF;
   char* cbuf = c.lds + (t & 1) * NT_BUF;
-  using P = NtPlan<POS>;
+  using P = NtPlan<POS, E>;
 #define NT_SPHASE_TAIL(Q, I0, J0, FA, FB)                                                  \
   if constexpr (P::issue(Q)) {                                                             \
     if constexpr (Q == 0) nt_stage_kt<LAY, 2>(c, so, q1, nbuf);                            \
@@ -947,7 +987,9 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_stream_kernel(NtArgs a,
   nt_s16x8 fa[2][4][2];
   nt_s16x8 fb[2][2][2];
 
-  // prologue: all of K-tile 0 and A0 + B0 of K-tile 1 (the one-tile kernel's halves -6 .. -1)
+  // prologue: all of K-tile 0 and A0 + B0 of K-tile 1 (the one-tile kernel's halves -6 .. -1),
+  // ALL waited for (the one-tile kernel waits for K-tile 0's A0 + B0 only): the stream's first
+  // K-tile then runs under any plan, NtPlan<3> included; once per launch
   NtKCur q1, q2;
   nt_kcur_set<LAY>(c, st, q1, 0);
   nt_stage_kt<LAY, 0>(c, so, q1, lds);
@@ -958,49 +1000,95 @@ __global__ void __launch_bounds__(NT_THREADS, 1) gemm_nt_stream_kernel(NtArgs a,
   if (st.total_k > 1) {
     nt_stage_kt<LAY, 0>(c, so, q1, lds + NT_BUF);
     nt_stage_kt<LAY, 1>(c, so, q1, lds + NT_BUF);
-    nt_vm<8>();
-  } else {
-    nt_vm<4>();
+  }
+  nt_vm<0>();
+  if constexpr (NtStreamE<EPI>::bias_loads > 0) {
+    // the compiler does not see the wait above (inline assembly) and would still count the first
+    // tile's bias loads as pending at every later touch of these registers, each a vmcnt(0):
+    // touch them here, where everything has landed anyway
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(epre.bias[j]));
   }
   q2 = q1;
   nt_kcur_next<LAY>(c, st, q2);                          // K-tile 2
   nt_bar();
   if (wr == 1) nt_bar();                                 // group 1 runs one barrier behind
 
-  // after each K-tile: when an output tile is complete, store it (the next tile's DMAs are
-  // already in flight), clear the accumulators and load the next tile's bias
-  int jt = 0, kin = 0;
-  auto finish_k = [&]() {
+  int jt = 0, t = 0;
+  auto next_k = [&]() {                                  // after each K-tile: advance both cursors
     q1 = q2;
     nt_kcur_next<LAY>(c, st, q2);
-    if (++kin != nk) return;
+    ++t;
+  };
+  // an output tile is complete: store it (the next tile's DMAs are already in flight) and clear
+  // the accumulators.  The next tile's bias is loaded BEFORE this tile's stores, into registers
+  // of its own: the compiler waits for a load where its result is first touched (a register
+  // copy is enough) with a count of the later vector-memory instructions IT knows -- the stores,
+  // not the DMAs, which are inline assembly.  Loaded after the stores, that wait came out as
+  // vmcnt(0) before or inside the next K-tile and drained every store and DMA in flight; loaded
+  // before them it lets all the stores stay outstanding.
+  auto finish_tile = [&]() {
     const long emrow = m0 + wr * 128 + (lane & 15), encol = n0 + wc * 64 + (lane >> 4) * 4;
+    constexpr bool HAS_BIAS = NtStreamE<EPI>::bias_loads > 0;
+    NtEpiPre<4> nxt;
+    if constexpr (HAS_BIAS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) nxt.bias[j] = epre.bias[j];
+    }
+    if (++jt < my_tiles) {
+      st.tile_origin(jt, m0, n0);
+      nt_preload_bias<EPI, 4>(a, n0 + wc * 64 + (lane >> 4) * 4, nxt);
+    }
     nt_epilogue<EPI, false, 4>(a, acc, emrow, encol, lane, 0, epre);
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    kin = 0;
-    if (++jt < my_tiles) {
-      st.tile_origin(jt, m0, n0);
-      nt_preload_bias<EPI, 4>(a, n0 + wc * 64 + (lane >> 4) * 4, epre);
+    if constexpr (HAS_BIAS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) epre.bias[j] = nxt.bias[j];
     }
   };
-  // steady state, then the two draining K-tiles of the whole stream (one ktile variant per
-  // loop: branching between variants inside one loop body spills the fragment registers)
+  // Tile by tile: the first K-tile of a tile steps over the previous epilogue's stores
+  // (NtPlan<3, E>), the others are the steady ones; the stream's last two K-tiles drain it
+  // (NtPlan<1>, <2>) and sit in its last tile (its last two tiles when nk == 1), kept out of the
+  // loop.  One K-tile variant per loop: branching between variants inside one loop body spills
+  // the fragment registers.
+  constexpr int E = NtStreamE<EPI>::value;
   const int T = st.total_k;
-  int t = 0;
-  for (; t < T - 2; ++t) {
-    nt_ktile_stream<0, LAY>(c, so, q1, q2, t, acc, fa, fb);
-    finish_k();
+  const int body_tiles = my_tiles - (nk >= 2 || my_tiles < 2 ? 1 : 2);
+  if (nk >= 2) {
+    while (jt < body_tiles) {
+      nt_ktile_stream<3, LAY, E>(c, so, q1, q2, t, acc, fa, fb);
+      next_k();
+      for (int k = 1; k < nk; ++k) {
+        nt_ktile_stream<0, LAY>(c, so, q1, q2, t, acc, fa, fb);
+        next_k();
+      }
+      finish_tile();
+    }
+    if (nk >= 3) {                                       // the last tile, up to the drain
+      nt_ktile_stream<3, LAY, E>(c, so, q1, q2, t, acc, fa, fb);
+      next_k();
+      for (int k = 1; k < nk - 2; ++k) {
+        nt_ktile_stream<0, LAY>(c, so, q1, q2, t, acc, fa, fb);
+        next_k();
+      }
+    }
+  } else {
+    while (jt < body_tiles) {                            // one K-tile per tile: the plain waits
+      nt_ktile_stream<0, LAY>(c, so, q1, q2, t, acc, fa, fb);
+      next_k();
+      finish_tile();
+    }
   }
   if (T >= 2) {
     nt_ktile_stream<1, LAY>(c, so, q1, q2, t, acc, fa, fb);
-    finish_k();
-    ++t;
+    next_k();
+    if (nk == 1) finish_tile();
   }
   nt_ktile_stream<2, LAY>(c, so, q1, q2, t, acc, fa, fb);
-  finish_k();
+  finish_tile();
   if (wr == 0) nt_bar();                                 // equal barrier counts for both groups
 }
 
@@ -1184,23 +1272,32 @@ static int nt_cu_count() {
 }
 
 // Streamed persistent GEMM: D[M,N] (+)= A[M,K] . B^T (b_kn = 0: B [N,K]; 1: B [K,N]) with
-// epilogue 0 (plain; accumulate: D += result) or 5 (+ bias[N]).  One workgroup per CU (or fewer when
-// there are fewer tiles).  Nonzero (nothing launched) when unsupported.
+// epilogue 0 (plain; accumulate: D += result), 5 (+ bias[N]), 6 (NT only: D = gelu(result + bias),
+// aux = gelu'(result + bias)) or 7 (NN only: D = result * aux, no column sums -- a caller that
+// wants them takes ct_gemm_nt).  One workgroup per CU (or fewer when there are fewer tiles).
+// Nonzero (nothing launched) when unsupported.
 extern "C" int ct_gemm_nt_stream(const void* A, long lda, const void* B, long ldb, void* D, long ldd, int M, int N,
-                                 int K, int epi, const void* bias, int b_kn, int wgs, int accumulate,
-                                 hipStream_t stream) {
+                                 int K, int epi, const void* bias, int b_kn, int wgs, int accumulate, void* aux,
+                                 long ldaux, hipStream_t stream) {
   if (M <= 0 || N <= 0 || K <= 0 || M % NT_BM || N % NT_BN || K % NT_BK) return 1;
   if (lda % 8 || ldb % 8 || ldd % 8 || lda < K || ldb < (b_kn ? N : K) || ldd < N) return 2;
   if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)D & 15)) return 3;
-  if (epi != 0 && epi != 5) return 6;
-  if (epi == 5 && (!bias || ((uintptr_t)bias & 7))) return 4;
+  if (epi != 0 && epi != 5 && epi != 6 && epi != 7) return 6;
+  if ((epi == 6 && b_kn) || (epi == 7 && !b_kn)) return 6;
+  // the bias is not optional where the epilogue loads one: NtStreamE counts its loads
+  if ((epi == 5 || epi == 6) && (!bias || ((uintptr_t)bias & 7))) return 4;
+  if ((epi == 6 || epi == 7) && (!aux || ((uintptr_t)aux & 15) || ldaux % 8 || ldaux < N)) return 4;
   const long tiles = (long)(M / NT_BM) * (N / NT_BN);
   if (tiles > (1L << 30)) return 5;
   const int P = (int)std::min<long>(tiles, wgs > 0 ? wgs : nt_cu_count());
   if (accumulate && epi != 0) return 6;
-  NtArgs a{(const bf16_t*)A, (const bf16_t*)B, (bf16_t*)D, (const bf16_t*)bias, nullptr, nullptr, nullptr,
-           nullptr, lda, ldb, ldd, 0, 0, M, N, K, accumulate ? 1 : 0};
-  if (epi == 5) {
+  NtArgs a{(const bf16_t*)A, (const bf16_t*)B, (bf16_t*)D, (const bf16_t*)bias, (bf16_t*)aux, nullptr, nullptr,
+           nullptr, lda, ldb, ldd, ldaux, 0, M, N, K, accumulate ? 1 : 0};
+  if (epi == 6) {
+    gemm_nt_stream_kernel<NT_EPI_BIAS_GELU_DAUX, 0><<<P, NT_THREADS, 0, stream>>>(a, P);
+  } else if (epi == 7) {
+    gemm_nt_stream_kernel<NT_EPI_MUL_AUX_BGRAD, 2><<<P, NT_THREADS, 0, stream>>>(a, P);
+  } else if (epi == 5) {
     if (b_kn) gemm_nt_stream_kernel<NT_EPI_BIAS, 2><<<P, NT_THREADS, 0, stream>>>(a, P);
     else gemm_nt_stream_kernel<NT_EPI_BIAS, 0><<<P, NT_THREADS, 0, stream>>>(a, P);
   } else {

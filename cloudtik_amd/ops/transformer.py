@@ -55,6 +55,33 @@ _FUSED_FFN_FWD = os.environ.get("CLOUDTIK_AMD_FUSED_FFN_FWD", "1") == "1"
 _STORE_DGELU = os.environ.get("CLOUDTIK_AMD_FFN_STORE_DGELU", "1") == "1"
 
 
+# The two fused FFN GEMMs (EPI 6 forward, EPI 7 data gradient) on the streamed persistent kernel
+# (csrc/gemm_nt.hip gemm_nt_stream_kernel) instead of the one-tile kernel: same K order, MFMA
+# order and epilogue code, so the results are bit-equal; no workgroup launch and cold prologue
+# per tile, and the epilogue's stores drain behind the next tile's MFMAs.  "0" neither site,
+# "fwd" FFN1, "dgrad" the data gradient, "1" both (each where the GEMM is large enough, below).
+# A module attribute: tests set it directly.
+# Kernel probe at 32768 tokens: FFN1 326 -> 285 us, data gradient 302 -> 265 us.  BERT-large step,
+# 13 interleaved rounds on four boxes (profiles/ffn_stream/SUMMARY.md): both sites on beat both
+# off in every round by 0.90-1.05 ms/step (e.g. 70.52 -> 69.46); one site alone gains 0.3-0.7 ms,
+# which is not clear of the off setting's round-to-round spread on every box.
+_STREAM_FFN = os.environ.get("CLOUDTIK_AMD_STREAM_FFN", "1")
+# A site that is on takes the streamed kernel when the GEMM has more 256 x 256 output tiles than
+# this (None: the device's CU count), i.e. when some workgroup walks more than one tile.  With one
+# tile per workgroup there is no tile boundary to stream across: the streamed kernel is then the
+# one-tile kernel with a prologue that waits for all of its DMAs, and the one-tile kernel stays.
+_STREAM_FFN_MIN_TILES = None
+
+
+def _stream_ffn(site, T, F, device) -> bool:
+    if _STREAM_FFN != "1" and _STREAM_FFN != site:
+        return False
+    floor = _STREAM_FFN_MIN_TILES
+    if floor is None:
+        floor = torch.cuda.get_device_properties(device).multi_processor_count
+    return (T // 256) * (F // 256) > floor
+
+
 def _fused_ffn1(C, x2, W1, b1f):
     """(aux, h, kind): h = gelu(x2 W1^T + b1f); aux = gelu'(x2 W1^T + b1f) (kind "dgelu") or
     the biased pre-activation itself (kind "z").  None when unsupported."""
@@ -65,6 +92,9 @@ def _fused_ffn1(C, x2, W1, b1f):
     aux = torch.empty(T, F, device=x2.device, dtype=x2.dtype)
     h = torch.empty_like(aux)
     epi = 6 if _STORE_DGELU else 1
+    if (epi == 6 and _stream_ffn("fwd", T, F, x2.device)
+            and C.gemm_nt_stream(x2, W1, h, b1f, False, 0, False, epi=6, aux=aux)):
+        return aux, h, "dgelu"
     if not C.gemm_nt(x2, W1, h, epi, False, b1f, aux, None):
         return None
     return aux, h, ("dgelu" if epi == 6 else "z")
@@ -121,6 +151,9 @@ def _fused_ffn_dgrad(C, df, W2, z, b1f, db1f, dgelu=False):
         return None
     dz = torch.empty_like(z)
     if db1f is None:                                   # no bias-gradient sums in the epilogue
+        if (dgelu and _stream_ffn("dgrad", T, F, z.device)
+                and C.gemm_nt_stream(df, W2, dz, None, True, 0, False, epi=7, aux=z)):
+            return dz
         return dz if C.gemm_nn(df, W2, dz, 7 if dgelu else 2, False, None if dgelu else b1f, z, None) else None
     direct = db1f.dtype == torch.bfloat16 and db1f.is_contiguous()
     rows = _DB_ROWS if direct else 1
