@@ -38,10 +38,13 @@ def _bad_int(v, lowest):
 
 def build_config(model_name: str, dataset, batch_size: int, accuracy_criterion_relative, exit_policy_timeout,
                  exit_policy_max_trials, tuning_random_seed, tuning_workspace, approach=APPROACH,
-                 calibration_sampling_size=100) -> dict:
-    loader = lambda: {"batch_size": batch_size,
-                      "dataset": {"text_classification": {"num_examples": len(dataset),
-                                                          "max_length": int(dataset.ids.shape[1])}}}
+                 calibration_sampling_size=100, describe_dataset=None) -> dict:
+    """``describe_dataset(dataset)`` gives the ``dataset`` entry of the two dataloader blocks; the
+    default describes a ``TextClassificationDataset``."""
+    if describe_dataset is None:
+        describe_dataset = lambda d: {"text_classification": {"num_examples": len(d),
+                                                              "max_length": int(d.ids.shape[1])}}
+    loader = lambda: {"batch_size": batch_size, "dataset": describe_dataset(dataset)}
     tuning = {"accuracy_criterion": {"relative": accuracy_criterion_relative},
               "exit_policy": {"timeout": exit_policy_timeout, "max_trials": exit_policy_max_trials},
               "random_seed": tuning_random_seed}
@@ -80,6 +83,44 @@ def _batch_size(cfg: dict, section: str, default: int) -> int:
     return int(cfg.get("evaluation", {}).get(section, {}).get("dataloader", {}).get("batch_size") or default)
 
 
+def check_config_args(batch_size, accuracy_criterion_relative, exit_policy_timeout, exit_policy_max_trials,
+                      tuning_random_seed, tuning_workspace, approach, calibration_sampling_size,
+                      approaches=APPROACHES):
+    """The value checks of ``export_quantization_config`` (ValueError), shared by the text mixin
+    and the image workflow."""
+    if _bad_int(batch_size, 1) or isinstance(batch_size, bool):
+        raise ValueError(f"Invalid value for batch size ({batch_size}). Expected a positive integer.")
+    if (accuracy_criterion_relative and not isinstance(accuracy_criterion_relative, float)) or \
+            accuracy_criterion_relative is None or not (0.0 <= accuracy_criterion_relative <= 1.0):
+        raise ValueError(f"Invalid value for the accuracy criterion ({accuracy_criterion_relative}). "
+                         "Expected a float value between 0.0 and 1.0")
+    if _bad_int(exit_policy_timeout, 0):
+        raise ValueError(f"Invalid value for the exit policy timeout ({exit_policy_timeout}). "
+                         "Expected a positive integer or 0.")
+    if _bad_int(exit_policy_max_trials, 1):
+        raise ValueError(f"Invalid value for max trials ({exit_policy_max_trials}). "
+                         "Expected an integer greater than 0.")
+    if _bad_int(tuning_random_seed, 0):
+        raise ValueError(f"Invalid value for tuning random seed ({tuning_random_seed}). "
+                         "Expected a positive integer.")
+    if not isinstance(tuning_workspace, str):
+        raise ValueError("Invalid value for the tuning workspace directory. Expected a string.")
+    if approach not in approaches:
+        raise ValueError(f"Invalid value for the approach ({approach!r}). Expected one of {list(approaches)}.")
+    if _bad_int(calibration_sampling_size, 1) or isinstance(calibration_sampling_size, bool):
+        raise ValueError(f"Invalid value for the calibration sampling size ({calibration_sampling_size}). "
+                         "Expected a positive integer.")
+
+
+def write_config(cfg: dict, config_file_path: str):
+    import yaml
+    parent = os.path.dirname(config_file_path)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    with open(config_file_path, "w") as f:
+        yaml.safe_dump(cfg, f, sort_keys=False)
+
+
 class TextQuantizationMixin:
     """``export_quantization_config`` / ``quantize`` / ``benchmark`` of ``TextClassificationModel``
     and the reference-named aliases."""
@@ -105,39 +146,14 @@ class TextQuantizationMixin:
         if not isinstance(dataset, TextClassificationDataset):
             raise NotImplementedError("quantization has only been implemented for text classification models "
                                       "with a TextClassificationDataset")
-        if _bad_int(batch_size, 1) or isinstance(batch_size, bool):
-            raise ValueError(f"Invalid value for batch size ({batch_size}). Expected a positive integer.")
-        if (accuracy_criterion_relative and not isinstance(accuracy_criterion_relative, float)) or \
-                accuracy_criterion_relative is None or not (0.0 <= accuracy_criterion_relative <= 1.0):
-            raise ValueError(f"Invalid value for the accuracy criterion ({accuracy_criterion_relative}). "
-                             "Expected a float value between 0.0 and 1.0")
-        if _bad_int(exit_policy_timeout, 0):
-            raise ValueError(f"Invalid value for the exit policy timeout ({exit_policy_timeout}). "
-                             "Expected a positive integer or 0.")
-        if _bad_int(exit_policy_max_trials, 1):
-            raise ValueError(f"Invalid value for max trials ({exit_policy_max_trials}). "
-                             "Expected an integer greater than 0.")
-        if _bad_int(tuning_random_seed, 0):
-            raise ValueError(f"Invalid value for tuning random seed ({tuning_random_seed}). "
-                             "Expected a positive integer.")
-        if not isinstance(tuning_workspace, str):
-            raise ValueError("Invalid value for the tuning workspace directory. Expected a string.")
-        if approach not in APPROACHES:
-            raise ValueError(f"Invalid value for the approach ({approach!r}). Expected one of {list(APPROACHES)}.")
-        if _bad_int(calibration_sampling_size, 1) or isinstance(calibration_sampling_size, bool):
-            raise ValueError(f"Invalid value for the calibration sampling size ({calibration_sampling_size}). "
-                             "Expected a positive integer.")
+        check_config_args(batch_size, accuracy_criterion_relative, exit_policy_timeout, exit_policy_max_trials,
+                          tuning_random_seed, tuning_workspace, approach, calibration_sampling_size)
         if not tuning_workspace and os.getenv("OUTPUT_DIR", ""):
             tuning_workspace = os.path.join(os.environ["OUTPUT_DIR"], "nc_workspace")
         cfg = build_config(self.model_name, dataset, batch_size, accuracy_criterion_relative, exit_policy_timeout,
                            exit_policy_max_trials, tuning_random_seed, tuning_workspace, approach,
                            calibration_sampling_size)
-        import yaml
-        parent = os.path.dirname(config_file_path)
-        if parent:
-            os.makedirs(parent, exist_ok=True)
-        with open(config_file_path, "w") as f:
-            yaml.safe_dump(cfg, f, sort_keys=False)
+        write_config(cfg, config_file_path)
 
     def export_neural_compressor_config(self, config_file_path, dataset, batch_size, overwrite=False,
                                         resize_interpolation='bicubic', accuracy_criterion_relative=0.01,

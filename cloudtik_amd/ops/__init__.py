@@ -128,7 +128,7 @@ from .graph import CSR, SpMM, gbdt_histogram, gbdt_predict, spmm  # noqa: E402,F
 from .deform import (DeformConv, DeformRoIPooling, DeformRoIPoolingPack, ModulatedDeformConv,  # noqa: E402,F401
                      ModulatedDeformConvPack, deform_conv2d, deform_roi_pooling)
 from .rnnt import rnnt_loss, rnnt_loss_reference  # noqa: E402,F401
-from .quant import (layer_norm_quant, linear_i8, linear_i8_static, quantize_rows, quantize_static,  # noqa: E402,F401
-                    quantize_weight)
+from .quant import (conv2d_i8_static, fold_bn, layer_norm_quant, linear_i8, linear_i8_static,  # noqa: E402,F401
+                    quantize_rows, quantize_static, quantize_weight)
 from . import beam  # noqa: E402,F401
 from .beam import beam_step, beam_step_reference, beam_topk, cache_reorder_reference  # noqa: E402,F401

@@ -1,4 +1,4 @@
-// Bindings for the int8 quantization kernels (quant.hip).  Every constraint the kernels rely
+// Bindings for the int8 quantization kernels (quant.hip, quant_conv.hip).  Every constraint the kernels rely
 // on (dtype, contiguity, 16-byte alignment, K / N multiples, K range, matching sizes) is
 // checked here; a violated one raises and nothing is launched.
 #include <torch/extension.h>
@@ -15,6 +15,8 @@ int ct_layernorm_quant_i8(const void*, const void*, const void*, const void*, co
                           float, float, hipStream_t);
 int ct_gemm_i8_nt_static(const void*, const void*, float, const float*, const void*, void*, int, int, int, int, int,
                          float, hipStream_t);
+int ct_conv_i8_fwd(const void*, const void*, const float*, const float*, const void*, void*, int, int, int, int, int,
+                   int, int, int, float, float, float, int, int, hipStream_t);
 }
 
 namespace {
@@ -167,6 +169,54 @@ void gemm_i8_nt_static(at::Tensor a_q, double a_scale, at::Tensor w_q, at::Tenso
   TORCH_CHECK(rc == 0, "ct_gemm_i8_nt_static failed: ", rc);
 }
 
+// ------------------------------------------------------------------ int8 convolution
+#define QCL(x) TORCH_CHECK((x).is_cuda() && (x).dim() == 4 && (x).is_contiguous(at::MemoryFormat::ChannelsLast), \
+                           #x " must be a 4-D channels_last GPU tensor")
+
+// out [N, Co, Ho, Wo] = act(conv(x_q, w_q) * a_scale * w_scale[co] + bias[co] + res_q * res_scale), all
+// image tensors channels_last; a bf16 out takes the result, an int8 out its quantization with out_inv.
+// w_q [Co, R*R*Ci] has tap-major rows.
+void conv2d_i8_static(at::Tensor x_q, double a_scale, at::Tensor w_q, at::Tensor w_scale, at::Tensor bias,
+                      int64_t stride, int64_t padding, bool relu, c10::optional<at::Tensor> res_q, double res_scale,
+                      at::Tensor out, double out_inv) {
+  QCL(x_q); QCL(out); QCHECK(w_q); QCHECK(w_scale); QCHECK(bias);
+  QDT(x_q, at::kChar, "int8"); QDT(w_q, at::kChar, "int8");
+  QDT(w_scale, at::kFloat, "fp32"); QDT(bias, at::kFloat, "fp32");
+  QALIGN(x_q); QALIGN(w_q); QALIGN(out); QALIGN(w_scale); QALIGN(bias);
+  const bool i8 = out.scalar_type() == at::kChar;
+  TORCH_CHECK(i8 || out.scalar_type() == at::kBFloat16, "conv2d_i8_static: out must be bf16 or int8");
+  const int64_t N = x_q.size(0), Ci = x_q.size(1), H = x_q.size(2), W = x_q.size(3);
+  TORCH_CHECK(x_q.numel() > 0, "conv2d_i8_static: empty input");
+  TORCH_CHECK(w_q.dim() == 2, "conv2d_i8_static: w_q must be [Co, R*R*Ci]");
+  const int64_t Co = w_q.size(0), K = w_q.size(1);
+  TORCH_CHECK(Ci % 64 == 0 && Co >= 64 && Co % 64 == 0,
+              "conv2d_i8_static: Ci and Co must be multiples of 64, got ", Ci, " and ", Co);
+  TORCH_CHECK(K == Ci || K == 9 * Ci, "conv2d_i8_static: the filter must be 1x1 or 3x3 over all ", Ci,
+              " input channels (groups = 1), got rows of ", K);
+  const int64_t R = K == Ci ? 1 : 3;
+  TORCH_CHECK(K <= 32768, "conv2d_i8_static: R*S*Ci must be <= 32768, got ", K);
+  TORCH_CHECK(stride == 1 || stride == 2, "conv2d_i8_static: stride must be 1 or 2, got ", stride);
+  TORCH_CHECK(padding == R / 2, "conv2d_i8_static: padding must be R / 2 = ", R / 2, ", got ", padding);
+  TORCH_CHECK(w_scale.numel() == Co && bias.numel() == Co, "conv2d_i8_static: w_scale and bias must be [Co]");
+  const int64_t Ho = (H + 2 * padding - R) / stride + 1, Wo = (W + 2 * padding - R) / stride + 1;
+  TORCH_CHECK(out.size(0) == N && out.size(1) == Co && out.size(2) == Ho && out.size(3) == Wo,
+              "conv2d_i8_static: out must be [", N, ", ", Co, ", ", Ho, ", ", Wo, "]");
+  TORCH_CHECK(N * Ho * Wo <= 65535 * 128 && N * H * W <= INT32_MAX, "conv2d_i8_static: too many pixels");
+  const float sa = checked_factor(a_scale, "conv2d_i8_static: a_scale");
+  const float sr = checked_factor(res_scale, "conv2d_i8_static: res_scale");
+  const float inv = checked_factor(out_inv, "conv2d_i8_static: out_inv");
+  const void* r = nullptr;
+  if (res_q.has_value() && res_q->defined()) {
+    QCL(*res_q); QDT(*res_q, at::kChar, "int8"); QALIGN(*res_q);
+    TORCH_CHECK(res_q->sizes() == out.sizes(), "conv2d_i8_static: the residual must have the output's shape");
+    r = res_q->data_ptr();
+  }
+  int rc = ct_conv_i8_fwd(x_q.data_ptr(), w_q.data_ptr(), w_scale.data_ptr<float>(), bias.data_ptr<float>(), r,
+                          out.data_ptr(), (int)N, (int)H, (int)W, (int)Ci, (int)Co, (int)R, (int)stride, (int)padding,
+                          sa, sr, inv, relu ? 1 : 0, i8 ? 1 : 0, stream());
+  TORCH_CHECK(rc == 0, "ct_conv_i8_fwd failed: ", rc);
+}
+
 }  // namespace
 
 void register_quant(pybind11::module& m) {
@@ -177,6 +227,10 @@ void register_quant(pybind11::module& m) {
   m.def("gemm_i8_nt_static", &gemm_i8_nt_static, pybind11::arg("a_q"), pybind11::arg("a_scale"),
         pybind11::arg("w_q"), pybind11::arg("w_scale"), pybind11::arg("bias"), pybind11::arg("act"),
         pybind11::arg("out"), pybind11::arg("out_inv"));
+  m.def("conv2d_i8_static", &conv2d_i8_static, pybind11::arg("x_q"), pybind11::arg("a_scale"), pybind11::arg("w_q"),
+        pybind11::arg("w_scale"), pybind11::arg("bias"), pybind11::arg("stride"), pybind11::arg("padding"),
+        pybind11::arg("relu"), pybind11::arg("res_q"), pybind11::arg("res_scale"), pybind11::arg("out"),
+        pybind11::arg("out_inv"));
   m.def("quant_rows_i8", &quant_rows_i8);
   m.def("gemm_i8_nt", &gemm_i8_nt, pybind11::arg("a_q"), pybind11::arg("a_scale"), pybind11::arg("w_q"),
         pybind11::arg("w_scale"), pybind11::arg("bias"), pybind11::arg("act"), pybind11::arg("out"));

@@ -8,7 +8,8 @@ bit on the quantized tensors, and the int32 accumulation is exact on both.
 
 Static quantization (``quantize_static``, ``layer_norm_quant``, ``linear_i8_static``) applies the
 same rule against one calibrated range per tensor, so the cast is elementwise and fused into
-the kernel that produces the tensor.
+the kernel that produces the tensor.  ``conv2d_i8_static`` (csrc/quant_conv.hip) is the static int8
+convolution, with BatchNorm folded into its weights and bias (``fold_bn``).
 
 GPU tensors go to the HIP kernels (required; shapes outside their tiling raise), CPU tensors
 to ``ops.reference``.
@@ -137,3 +138,40 @@ def linear_i8_static(x: torch.Tensor, a_amax: float, w_q: torch.Tensor, w_scale:
     else:
         out = ref.linear_i8_static(a2, a_amax, w_q, w_scale, bias, act, out_amax, dtype or torch.float32)
     return out.view(*lead, N)
+
+
+# ------------------------------------------------------------------ static int8 convolution
+fold_bn = ref.fold_bn
+
+
+def conv2d_i8_static(x_q: torch.Tensor, a_amax: float, w_q: torch.Tensor, w_scale: torch.Tensor, bias: torch.Tensor,
+                     stride, padding, relu: bool, res_q: Optional[torch.Tensor] = None,
+                     res_amax: Optional[float] = None, out_amax: Optional[float] = None,
+                     dtype: Optional[torch.dtype] = None, dilation=1, groups=1) -> torch.Tensor:
+    """relu(conv(x_q, w_q) dequantized + bias + residual) with int8 operands and exact int32
+    accumulation.  ``x_q`` int8 [N, Ci, H, W] (channels_last on the GPU) holds values of range
+    ``a_amax``; ``w_q`` int8 [Co, R*R*Ci] are tap-major rows (``conv.weight_rows`` order) with fp32
+    ``w_scale`` [Co]; ``bias`` is fp32 [Co] (with ``fold_bn`` it carries the BatchNorm shift);
+    ``res_q`` int8 of the output's shape has range ``res_amax``.  The result is ``dtype`` (bf16 on
+    the GPU, fp32 by default on the CPU), or with ``out_amax`` that result quantized against the
+    range: int8, ready for the next convolution.
+
+    The GPU kernel takes Ci and Co multiples of 64, 1x1 and 3x3 filters, stride 1 or 2, padding
+    R // 2, groups = dilation = 1 and R*R*Ci <= 32768; anything else raises."""
+    if _pkg()._use_native(x_q, w_q):
+        R, stride, padding, Ho, Wo = ref.conv_geometry(x_q.shape, w_q.shape, stride, padding, dilation, groups)
+        if dtype not in (None, torch.bfloat16):
+            raise TypeError(f"conv2d_i8_static: the GPU kernel computes bf16, not {dtype}")
+        if (res_q is None) != (res_amax is None):
+            raise ValueError("conv2d_i8_static: a residual needs its range, and a range its residual")
+        a_scale, _ = ref.static_scales(a_amax)
+        res_scale = 0.0 if res_amax is None else ref.static_scales(res_amax)[0]
+        out_inv = 0.0 if out_amax is None else ref.static_scales(out_amax)[1]
+        out = torch.empty((x_q.shape[0], w_q.shape[0], Ho, Wo), device=x_q.device,
+                          dtype=torch.bfloat16 if out_amax is None else torch.int8,
+                          memory_format=torch.channels_last)
+        _pkg().require_native().conv2d_i8_static(x_q, a_scale, w_q, w_scale, bias, stride, padding, bool(relu), res_q,
+                                                 res_scale, out, out_inv)
+        return out
+    return ref.conv_i8_static(x_q, a_amax, w_q, w_scale, bias, stride, padding, relu, res_q, res_amax, out_amax,
+                              dtype or torch.float32, dilation, groups)

@@ -239,3 +239,96 @@ def linear_i8_static(a_q, a_amax, w_q, w_scale, bias=None, act=ACT_NONE, out_ama
     a_scale = torch.full((a_q.shape[0],), scale, dtype=torch.float32, device=a_q.device)
     y = dequant_epilogue(gemm_i8_nt_raw(a_q, w_q), a_scale, w_scale, bias, act, dtype)
     return y if out_amax is None else quantize_static(y, out_amax)
+
+
+# ------------------------------------------------------------------ static int8 convolution
+def _square(v, what) -> int:
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2 or v[0] != v[1]:
+            raise ValueError(f"conv_i8_static: {what} must be the same in both directions, got {tuple(v)}")
+        v = v[0]
+    return int(v)
+
+
+def conv_geometry(x_shape, w_rows_shape, stride, padding, dilation=1, groups=1):
+    """(R, stride, padding, Ho, Wo) of a square convolution given by its tap-major weight rows
+    [Co, R*R*Ci]; raises ValueError for rows that are no whole square filter over all Ci channels
+    (a grouped weight is not), and for a dilation or a group count other than 1."""
+    if _square(dilation, "dilation") != 1 or int(groups) != 1:
+        raise ValueError(f"conv_i8_static: dilation and groups must be 1, got {dilation} and {groups}")
+    stride, padding = _square(stride, "stride"), _square(padding, "padding")
+    if len(x_shape) != 4 or len(w_rows_shape) != 2:
+        raise ValueError("conv_i8_static: expected x [N, Ci, H, W] and weight rows [Co, R*R*Ci]")
+    ci, K = x_shape[1], w_rows_shape[1]
+    R = math.isqrt(K // ci) if ci > 0 and K % ci == 0 else 0
+    if R < 1 or R * R * ci != K:
+        raise ValueError(f"conv_i8_static: rows of {K} are no square filter over {ci} input channels")
+    if stride < 1 or padding < 0:
+        raise ValueError(f"conv_i8_static: bad stride {stride} / padding {padding}")
+    Ho, Wo = (x_shape[2] + 2 * padding - R) // stride + 1, (x_shape[3] + 2 * padding - R) // stride + 1
+    if Ho < 1 or Wo < 1:
+        raise ValueError("conv_i8_static: the filter does not fit the image")
+    return R, stride, padding, Ho, Wo
+
+
+def conv_i8_acc(x_q, w_q, stride, padding):
+    """The exact int32 accumulators [N, Co, Ho, Wo] of an int8 convolution: x_q [N, Ci, H, W],
+    w_q [Co, R*R*Ci] tap-major rows ([Co][R][S][Ci]).  int64 unfold + matmul (fp32 is not exact:
+    one K = 4608 dot product of int8 products passes 2^24)."""
+    R, stride, padding, Ho, Wo = conv_geometry(x_q.shape, w_q.shape, stride, padding)
+    N, ci, H, W = x_q.shape
+    co = w_q.shape[0]
+    xp = F.pad(x_q.to(torch.int64), (padding, padding, padding, padding))
+    cols = []
+    for r in range(R):                                    # tap-major, channel-minor: the rows' order
+        for s in range(R):
+            cols.append(xp[:, :, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride])
+    a = torch.stack(cols, 1).reshape(N, R * R * ci, Ho * Wo)          # [N, K, P]
+    acc = torch.matmul(w_q.to(torch.int64).unsqueeze(0), a)           # [N, Co, P]
+    return acc.reshape(N, co, Ho, Wo).to(torch.int32)
+
+
+def conv_i8_static(x_q, a_amax, w_q, w_scale, bias, stride, padding, relu, res_q=None, res_amax=None,
+                   out_amax=None, dtype=torch.float32, dilation=1, groups=1):
+    """Static int8 convolution with the epilogue of csrc/quant_conv.hip, one fp32 operation at a
+    time and in its order:
+
+        f = acc * (a_scale * w_scale[co]);  f = f + bias[co];  f = f + res_q * res_scale;
+        f = max(f, 0) if relu;  y = f rounded to ``dtype``
+
+    and, with ``out_amax``, ``quantize_static(y, out_amax)`` (int8) in place of y.  ``x_q`` is
+    int8 [N, Ci, H, W], ``w_q`` int8 [Co, R*R*Ci] tap-major rows, ``w_scale`` and ``bias`` fp32
+    [Co] (the bias carries the folded BatchNorm shift), ``res_q`` int8 of the output's shape with
+    its range ``res_amax``."""
+    conv_geometry(x_q.shape, w_q.shape, stride, padding, dilation, groups)
+    if x_q.dtype != torch.int8 or w_q.dtype != torch.int8:
+        raise TypeError("conv_i8_static: x_q and w_q must be int8")
+    if (res_q is None) != (res_amax is None):
+        raise ValueError("conv_i8_static: a residual needs its range, and a range its residual")
+    a_scale, _ = static_scales(a_amax)
+    acc = conv_i8_acc(x_q, w_q, stride, padding)
+    one = lambda v: torch.full((), v, dtype=torch.float32, device=acc.device)
+    f = acc.to(torch.float32) * (one(a_scale) * w_scale.float()).view(1, -1, 1, 1)
+    f = f + bias.float().view(1, -1, 1, 1)
+    if res_q is not None:
+        if res_q.dtype != torch.int8 or res_q.shape != f.shape:
+            raise ValueError("conv_i8_static: the residual must be int8 and have the output's shape")
+        f = f + res_q.to(torch.float32) * one(static_scales(res_amax)[0])
+    if relu:
+        f = torch.clamp_min(f, 0.0)
+    y = f.to(dtype)
+    if x_q.is_contiguous(memory_format=torch.channels_last):
+        y = y.contiguous(memory_format=torch.channels_last)
+    return y if out_amax is None else quantize_static(y, out_amax)
+
+
+def fold_bn(conv_weight, bn):
+    """Fold an eval-mode BatchNorm into the bias-free convolution in front of it:
+    (w_folded fp32 [Co, R*S*Ci] tap-major rows, bias fp32 [Co]) with
+    bn(conv(x, w)) == conv(x, w_folded) + bias.  fp32 on the host, from the running statistics;
+    ``bn`` is anything with weight, bias, running_mean, running_var and eps."""
+    w = conv_weight.detach().float().cpu()
+    g = bn.weight.detach().float().cpu() * torch.rsqrt(bn.running_var.detach().float().cpu() + bn.eps)
+    rows = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1) * g.unsqueeze(1)
+    bias = bn.bias.detach().float().cpu() - bn.running_mean.detach().float().cpu() * g
+    return rows.contiguous(), bias.contiguous()
