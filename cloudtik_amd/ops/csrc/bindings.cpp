@@ -472,9 +472,17 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
   bshd_strides(dO, dos, "dO"); bshd_strides(dq, dqs, "dq"); bshd_strides(dk, dks, "dk"); bshd_strides(dv, dvs, "dv");
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
   TORCH_CHECK(dO.sizes() == o.sizes() && dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes());
-  TORCH_CHECK(lse.numel() == (long)B * H * Sq);
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
+  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
+  // the kernels read lse as a dense fp32 [B*H, Sq] and key_bias as fp32 rows of Sk keys
+  CHECK_F32(lse); CHECK_CUDA(lse);
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == (long)B * H * Sq, "lse must be contiguous fp32 [B*H, Sq]");
   const float* kb = nullptr; long kb_sb = 0;
-  if (key_bias.has_value() && key_bias->defined()) { kb = key_bias->data_ptr<float>(); kb_sb = key_bias->stride(0); }
+  if (key_bias.has_value() && key_bias->defined()) {
+    CHECK_F32(*key_bias); CHECK_CUDA(*key_bias);
+    TORCH_CHECK(key_bias->dim() == 2 && key_bias->size(0) == B && key_bias->size(1) == Sk && key_bias->stride(1) == 1);
+    kb = key_bias->data_ptr<float>(); kb_sb = key_bias->stride(0);
+  }
   auto fo = q.options().dtype(at::kFloat);
   auto delta = at::empty({(long)B * H * Sq}, fo);
   at::Tensor dq_acc;
