@@ -14,7 +14,8 @@ so inference never materialises an [H, Sq, Sk] bias; cross-attention uses the MF
 with the per-key padding mask; training self-attention (which needs the bias gradient) uses
 SDPA with the gathered bias; the training loss is the fused linear + cross-entropy HIP
 kernel over the 32128-token vocabulary; generation keeps a per-layer KV cache and replays
-the decode step as a HIP graph, greedy or with beam search (``ops/beam.py``, ``csrc/beam.hip``).
+the decode step as a HIP graph, greedy, with beam search (``ops/beam.py``, ``csrc/beam.hip``) or
+sampling (``ops/sampling.py``, ``csrc/sampling.hip``).
 """
 from __future__ import annotations
 
@@ -30,6 +31,7 @@ import torch.nn.functional as F
 
 from cloudtik_amd import ops
 from cloudtik_amd.ops import beam as beam_ops
+from cloudtik_amd.ops import sampling as sample_ops
 
 logger = logging.getLogger(__name__)
 
@@ -286,7 +288,9 @@ class T5ForConditionalGeneration(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 32,
                  use_graph: Optional[bool] = None, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping: bool = False, return_scores: bool = False, trace: Optional[list] = None):
+                 early_stopping: bool = False, return_scores: bool = False, trace: Optional[list] = None,
+                 do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                 repetition_penalty: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None):
         """Greedy decoding with a KV cache (self-attention K/V grow; cross K/V computed once).
 
         On the GPU the decode step is captured once into a HIP graph over a static KV cache
@@ -300,17 +304,52 @@ class T5ForConditionalGeneration(nn.Module):
         step runs at batch B * num_beams inside the same kind of graph, with the bookkeeping
         in the beam kernels (``_generate_beam_static``); ``use_graph=False``, a ``trace`` list and
         the CPU run the eager reference loop, which appends every step's 2K candidate scores
-        [B, 2K] to ``trace``."""
+        [B, 2K] to ``trace``.  ``num_return_sequences`` = N <= ``num_beams`` returns the N best
+        finished hypotheses [B * N, max_new_tokens], item-major (rows b * N .. b * N + N - 1 belong
+        to input b), and their scores [B * N].
+
+        ``do_sample`` draws every token instead (``ops.sampling`` states the rule: repetition
+        penalty, temperature, top-k, top-p as the HF logits processors apply them, then one draw
+        per row and step from a Philox stream keyed by ``seed``).  It needs ``num_beams`` = 1 and
+        returns N = ``num_return_sequences`` independent samples per input, [B * N,
+        max_new_tokens], item-major, pad after EOS.  ``top_k`` = 0 (or >= the vocabulary) and
+        ``top_p`` = 1 are off.  ``seed`` is an int in [0, 2**63); None draws one from torch's
+        default CPU generator, so ``torch.manual_seed`` makes a program reproducible.  The same
+        seed, arguments and model give the same tokens replayed, eager on the static step, or
+        called again.  On the GPU the step runs at batch B * N inside a graph that ends in the
+        sampling kernel (``_generate_sample_static``) and reads the seed from the device, so one
+        capture per (temperature, top_k, top_p, repetition_penalty) serves every seed;
+        ``use_graph=False`` runs the eager loop on the growing-cache decoder, ended by the same
+        kernel on the GPU and by the reference on the CPU.  Without ``do_sample`` the sampling
+        arguments must be at their defaults."""
         if use_graph is None:
             use_graph = input_ids.is_cuda and os.environ.get("CLOUDTIK_AMD_T5_GRAPH", "1") == "1"
         beam_ops.check_beam_args(num_beams, self.cfg.vocab_size, early_stopping)
+        sample_ops.check_sample_args(temperature, top_k, top_p, repetition_penalty, num_return_sequences, seed)
+        N = num_return_sequences
+        if do_sample:
+            if num_beams != 1:
+                raise ValueError("do_sample needs num_beams = 1 (beam sampling is not supported)")
+            if return_scores or trace is not None:
+                raise ValueError("return_scores and trace belong to beam search (num_beams > 1)")
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            if use_graph and input_ids.is_cuda:
+                return self._generate_sample_static(input_ids, attention_mask, max_new_tokens, N, seed, temperature,
+                                                    top_k, top_p, repetition_penalty)
+            return self._generate_sample_eager(input_ids, attention_mask, max_new_tokens, N, seed, temperature,
+                                               top_k, top_p, repetition_penalty)
+        if temperature != 1.0 or top_k != 0 or top_p != 1.0 or repetition_penalty != 1.0 or seed is not None:
+            raise ValueError("temperature, top_k, top_p, repetition_penalty and seed belong to sampling (do_sample=True)")
+        if N > num_beams:
+            raise ValueError(f"num_return_sequences = {N} needs do_sample=True or num_beams >= {N}, got num_beams = {num_beams}")
         if num_beams > 1:
             if use_graph and input_ids.is_cuda and trace is None:
                 seq, score = self._generate_beam_static(input_ids, attention_mask, max_new_tokens, num_beams,
-                                                        length_penalty, early_stopping)
+                                                        length_penalty, early_stopping, num_return=N)
             else:
                 seq, score = self._generate_beam_eager(input_ids, attention_mask, max_new_tokens, num_beams,
-                                                       length_penalty, early_stopping, trace)
+                                                       length_penalty, early_stopping, trace, num_return=N)
             return (seq, score) if return_scores else seq
         if return_scores or trace is not None:
             raise ValueError("return_scores and trace belong to beam search (num_beams > 1)")
@@ -432,7 +471,8 @@ class T5ForConditionalGeneration(nn.Module):
 
     # ------------------------------------------------------------------------- beam search
     @torch.no_grad()
-    def _generate_beam_eager(self, input_ids, attention_mask, max_new, K, length_penalty, early_stopping, trace=None):
+    def _generate_beam_eager(self, input_ids, attention_mask, max_new, K, length_penalty, early_stopping, trace=None,
+                             num_return: int = 1):
         """The reference beam loop, any device and dtype: the growing-cache decoder at batch
         B * K and ``beam_step_reference`` / ``cache_reorder_reference`` after every step."""
         cfg, dev = self.cfg, input_ids.device
@@ -453,11 +493,21 @@ class T5ForConditionalGeneration(nn.Module):
             for c in caches:                       # cross K/V are the same for every beam of an item
                 c["self"] = tuple(beam_ops.cache_reorder_reference(c["self"], beam_idx))
             cur = nxt[:, None]
-        return state["fin_seq"][:, 0].clone(), state["fin_score"][:, 0].clone()
+        return self._best_finished(state, num_return)
+
+    @staticmethod
+    def _best_finished(state, n: int):
+        """The n best finished hypotheses and their scores: [B, T] and [B] for n = 1, else flattened
+        item-major to [B * n, T] and [B * n]."""
+        seq, score = state["fin_seq"], state["fin_score"]
+        if n == 1:
+            return seq[:, 0].clone(), score[:, 0].clone()
+        return seq[:, :n].reshape(-1, seq.shape[2]).clone(), score[:, :n].reshape(-1).clone()
 
     @torch.no_grad()
     def _generate_beam_static(self, input_ids, attention_mask, max_new, K, length_penalty=1.0, early_stopping=False,
-                              fused: bool = True, graph: bool = True, trace=None, select: str = "sort"):
+                              fused: bool = True, graph: bool = True, trace=None, select: str = "sort",
+                              num_return: int = 1):
         """Beam search over the static-cache decode step at batch B * K.  ``fused``: the beam
         kernels do the bookkeeping (else the PyTorch reference does, on the same step, so both
         see the same logits); ``graph``: two captured graphs, one per cache parity, are replayed
@@ -487,8 +537,7 @@ class T5ForConditionalGeneration(nn.Module):
         for t in range(T):
             st["steps"][t & 1]()
         st["trace"][0] = None
-        state = st["state"]
-        return state["fin_seq"][:, 0].clone(), state["fin_score"][:, 0].clone()
+        return self._best_finished(st["state"], num_return)
 
     def _capture_beam_decode(self, B, S, T, dtype, dev, masked, K, length_penalty, early_stopping, fused, graph,
                              select):
@@ -556,6 +605,111 @@ class T5ForConditionalGeneration(nn.Module):
         # "step" keeps what only the captured kernels still use (caches, pointer tables) allocated
         return {"steps": steps, "cross": cross, "enc_bias": enc_bias, "state": state, "reset": reset, "trace": trace,
                 "step": step}
+
+    # ---------------------------------------------------------------------------- sampling
+    @torch.no_grad()
+    def _generate_sample_eager(self, input_ids, attention_mask, max_new, N, seed, temperature=1.0, top_k=0, top_p=1.0,
+                               repetition_penalty=1.0):
+        """The eager sampling loop, any device and dtype: the growing-cache decoder at batch B * N,
+        and after every step ``sample_step_reference`` on the CPU or the sampling kernel on the GPU."""
+        cfg, dev = self.cfg, input_ids.device
+        R, T = input_ids.shape[0] * N, max_new
+        enc, _ = self.encoder(input_ids, attention_mask)
+        enc = enc.repeat_interleave(N, 0)
+        mask = attention_mask.repeat_interleave(N, 0) if attention_mask is not None else None
+        out = torch.full((R, T), cfg.pad_token_id, dtype=torch.long, device=dev)
+        done = torch.zeros(R, dtype=torch.bool, device=dev)
+        cur = torch.full((R, 1), cfg.decoder_start_token_id, dtype=torch.long, device=dev)
+        pos = torch.zeros(1, dtype=torch.long, device=dev)
+        seed_t = torch.tensor([seed], dtype=torch.long, device=dev)
+        rule = (cfg.decoder_start_token_id, cfg.eos_token_id, cfg.pad_token_id, temperature, top_k, top_p,
+                repetition_penalty)
+        caches = None
+        for t in range(T):
+            dec, caches = self.decoder(cur, enc=enc, enc_mask=mask, caches=caches, offset=t)
+            logits = self.logits(dec[:, -1])
+            if dev.type == "cuda":
+                sample_ops.sample_step(logits.contiguous(), out, done, cur, pos, seed_t, *rule)
+            else:
+                out, done, cur, pos = sample_ops.sample_step_reference(logits, out, done, cur, pos, seed_t, *rule)[:4]
+        return out
+
+    @torch.no_grad()
+    def _generate_sample_static(self, input_ids, attention_mask, max_new, N, seed, temperature=1.0, top_k=0,
+                                top_p=1.0, repetition_penalty=1.0, graph: bool = True):
+        """Sampling over the static-cache decode step at batch R = B * N, ended by the sampling
+        kernel.  ``graph``: the captured step is replayed (else the same step runs eagerly).
+        Captures are cached like the greedy ones, additionally by the sampling parameters, which
+        are launch arguments; the seed is a device tensor ``reset`` rewrites, so it is not in the
+        key."""
+        dev = input_ids.device
+        B, S, T = input_ids.shape[0], input_ids.shape[1], max_new
+        R = B * N
+        enc, _ = self.encoder(input_ids, attention_mask)
+        masked = attention_mask is not None
+        key = ("sample", R, S, T, masked, str(dev), float(temperature), int(top_k), float(top_p),
+               float(repetition_penalty), graph)
+        cache = getattr(self, "_graphs", None)
+        if cache is None:
+            cache = self._graphs = {}
+        st = cache.get(key)
+        if st is None:
+            st = cache[key] = self._capture_sample_decode(R, S, T, enc.dtype, dev, masked, float(temperature),
+                                                          int(top_k), float(top_p), float(repetition_penalty), graph)
+        for i, b in enumerate(self.decoder.blocks):     # cross K/V: expanded to B * N rows once per call
+            st["cross"][i][0].copy_(b.ca._split(b.ca.k(enc)).repeat_interleave(N, 0))
+            st["cross"][i][1].copy_(b.ca._split(b.ca.v(enc)).repeat_interleave(N, 0))
+        if masked:
+            st["enc_bias"].copy_(((1.0 - attention_mask.float()) * -1e9).repeat_interleave(N, 0))
+        st["reset"](seed)
+        for _ in range(T):
+            st["run"]()
+        return st["out"].clone()
+
+    def _capture_sample_decode(self, R, S, T, dtype, dev, masked, temperature, top_k, top_p, repetition_penalty,
+                               graph):
+        cfg = self.cfg
+        H, D = cfg.num_heads, cfg.d_kv
+        dec = self.decoder
+        kc = [torch.zeros(R, T, H, D, dtype=dtype, device=dev) for _ in dec.blocks]
+        vc = [torch.zeros(R, T, H, D, dtype=dtype, device=dev) for _ in dec.blocks]
+        cross = [(torch.zeros(R, S, H, D, dtype=dtype, device=dev), torch.zeros(R, S, H, D, dtype=dtype, device=dev))
+                 for _ in dec.blocks]
+        enc_bias = torch.zeros(R, S, device=dev) if masked else None
+        cur = torch.full((R, 1), cfg.decoder_start_token_id, dtype=torch.long, device=dev)
+        pos = torch.zeros(1, dtype=torch.long, device=dev)
+        seed = torch.zeros(1, dtype=torch.long, device=dev)
+        out = torch.full((R, T), cfg.pad_token_id, dtype=torch.long, device=dev)
+        done = torch.zeros(R, dtype=torch.bool, device=dev)
+        slots = torch.arange(T, device=dev)
+        rule = (cfg.decoder_start_token_id, cfg.eos_token_id, cfg.pad_token_id, temperature, top_k, top_p,
+                repetition_penalty)
+
+        def step():
+            x = self._decode_step_static(cur, pos, slots, kc, vc, cross, enc_bias)
+            sample_ops.sample_step(self.logits(x[:, -1]), out, done, cur, pos, seed, *rule)
+
+        def reset(seed_value=0):
+            seed.fill_(seed_value)
+            cur.fill_(cfg.decoder_start_token_id)
+            pos.zero_()
+            out.fill_(cfg.pad_token_id)
+            done.zero_()
+
+        run = step
+        if graph:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):      # warm up (lazy inits, library handles) off the capture
+                step()
+            torch.cuda.current_stream().wait_stream(side)
+            reset()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                step()
+            run = g.replay
+        # "step" keeps the buffers only the captured kernels still use (the caches) allocated
+        return {"run": run, "cross": cross, "enc_bias": enc_bias, "out": out, "reset": reset, "step": step}
 
     # --------------------------------------------------------------------- pretrained weights
     @classmethod

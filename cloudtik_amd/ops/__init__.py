@@ -132,3 +132,5 @@ from .quant import (conv2d_i8_static, fold_bn, layer_norm_quant, linear_i8, line
                     quantize_rows, quantize_static, quantize_weight)
 from . import beam  # noqa: E402,F401
 from .beam import beam_step, beam_step_reference, beam_topk, cache_reorder_reference  # noqa: E402,F401
+from . import sampling  # noqa: E402,F401
+from .sampling import sample_step, sample_step_reference  # noqa: E402,F401

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Greedy and beam-search generation with T5, from a local checkpoint directory or random init.
+"""Greedy, beam-search and sampled generation with T5, from a local checkpoint directory or random init.
 
     python examples/ai/t5_generate.py                                   # t5-small topology, random weights
     python examples/ai/t5_generate.py --checkpoint /models/t5-small --text "translate English to German: Hello"
     python examples/ai/t5_generate.py --num-beams 4 --length-penalty 0.6 --early-stopping
+    python examples/ai/t5_generate.py --do-sample --top-k 50 --top-p 0.95 --temperature 0.8 --num-return-sequences 3 --seed 7
 
 ``--checkpoint`` is a directory holding ``config.json`` and ``model.safetensors`` or
 ``pytorch_model.bin`` (nothing is downloaded).  With a ``spiece.model`` in it and the
@@ -54,6 +55,13 @@ def main():
     ap.add_argument("--num-beams", type=int, default=4)
     ap.add_argument("--length-penalty", type=float, default=1.0)
     ap.add_argument("--early-stopping", action="store_true")
+    ap.add_argument("--do-sample", action="store_true", help="also draw samples (the flags below)")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0, help="0: off")
+    ap.add_argument("--top-p", type=float, default=1.0, help="1: off")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--num-return-sequences", type=int, default=1, help="samples per source")
+    ap.add_argument("--seed", type=int, default=None, help="sampling seed (default: from torch's generator)")
     a = ap.parse_args()
 
     gpu = torch.cuda.is_available()
@@ -75,6 +83,14 @@ def main():
     for i in range(ids.shape[0]):
         print(f"[{i}] greedy: {show(greedy[i])}")
         print(f"[{i}] beam {a.num_beams} (score {float(score[i]):.4f}): {show(beam[i])}")
+    if a.do_sample:
+        n = a.num_return_sequences
+        samples = model.generate(ids, mask, max_new_tokens=a.max_new_tokens, do_sample=True, temperature=a.temperature,
+                                 top_k=a.top_k, top_p=a.top_p, repetition_penalty=a.repetition_penalty,
+                                 num_return_sequences=n, seed=a.seed)
+        for i in range(ids.shape[0]):
+            for j in range(n):                     # rows i * n .. i * n + n - 1 belong to source i
+                print(f"[{i}] sample {j}: {show(samples[i * n + j])}")
 
 
 if __name__ == "__main__":
