@@ -15,7 +15,9 @@ with the per-key padding mask; training self-attention (which needs the bias gra
 SDPA with the gathered bias; the training loss is the fused linear + cross-entropy HIP
 kernel over the 32128-token vocabulary; generation keeps a per-layer KV cache and replays
 the decode step as a HIP graph, greedy, with beam search (``ops/beam.py``, ``csrc/beam.hip``) or
-sampling (``ops/sampling.py``, ``csrc/sampling.hip``).
+sampling (``ops/sampling.py``, ``csrc/sampling.hip``), each with the history-dependent token bans of
+``no_repeat_ngram_size``, ``min_length`` and ``bad_words_ids`` (``ops/constrain.py``,
+``csrc/constrain.hip``).
 """
 from __future__ import annotations
 
@@ -31,6 +33,7 @@ import torch.nn.functional as F
 
 from cloudtik_amd import ops
 from cloudtik_amd.ops import beam as beam_ops
+from cloudtik_amd.ops import constrain as constrain_ops
 from cloudtik_amd.ops import sampling as sample_ops
 
 logger = logging.getLogger(__name__)
@@ -71,6 +74,39 @@ class T5Config:
                     relative_attention_num_buckets=8, relative_attention_max_distance=16, dropout_rate=0.0)
         base.update(kw)
         return cls(**base)
+
+
+_TASK_PASS_THROUGH = ("min_length", "no_repeat_ngram_size", "num_beams", "length_penalty", "early_stopping")
+
+
+def generate_kwargs_for_task(config, task: str):
+    """The generation settings a HF T5 config ships for ``task`` (``task_specific_params[task]``, such as
+    "summarization"), as ``(kwargs, prefix)``: keyword arguments of ``T5ForConditionalGeneration.generate``
+    and the text the task puts in front of its source.  ``config`` is a config of the library, a
+    dict, or the path of a local ``config.json``.  ``max_length`` counts the start token, so it
+    becomes ``max_new_tokens = max_length - 1``; ``min_length``, ``no_repeat_ngram_size``,
+    ``num_beams``, ``length_penalty`` and ``early_stopping`` pass through; a setting ``generate``
+    does not have raises ValueError."""
+    if isinstance(config, (str, os.PathLike)):
+        import json
+        with open(config) as f:
+            config = json.load(f)
+    elif not isinstance(config, dict):
+        config = config.to_dict()
+    tasks = config.get("task_specific_params") or {}
+    if task not in tasks:
+        raise KeyError(f"the config has no task_specific_params[{task!r}] (it has {sorted(tasks)})")
+    kwargs, prefix = {}, ""
+    for name, value in tasks[task].items():
+        if name == "prefix":
+            prefix = value
+        elif name == "max_length":
+            kwargs["max_new_tokens"] = int(value) - 1
+        elif name in _TASK_PASS_THROUGH:
+            kwargs[name] = value
+        else:
+            raise ValueError(f"task_specific_params[{task!r}] sets {name!r}, which generate does not support")
+    return kwargs, prefix
 
 
 def relative_position_bucket(rel: torch.Tensor, bidirectional: bool, num_buckets: int, max_distance: int):
@@ -290,7 +326,9 @@ class T5ForConditionalGeneration(nn.Module):
                  use_graph: Optional[bool] = None, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping: bool = False, return_scores: bool = False, trace: Optional[list] = None,
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                 repetition_penalty: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None):
+                 repetition_penalty: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
+                 no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, min_length: int = 0,
+                 bad_words_ids: Optional[List[List[int]]] = None):
         """Greedy decoding with a KV cache (self-attention K/V grow; cross K/V computed once).
 
         On the GPU the decode step is captured once into a HIP graph over a static KV cache
@@ -321,11 +359,22 @@ class T5ForConditionalGeneration(nn.Module):
         capture per (temperature, top_k, top_p, repetition_penalty) serves every seed;
         ``use_graph=False`` runs the eager loop on the growing-cache decoder, ended by the same
         kernel on the GPU and by the reference on the CPU.  Without ``do_sample`` the sampling
-        arguments must be at their defaults."""
+        arguments must be at their defaults.
+
+        ``no_repeat_ngram_size``, ``min_new_tokens``, ``min_length`` (the library's: it counts the
+        start token, so the minimum is ``max(min_new_tokens, min_length - 1)`` new tokens) and
+        ``bad_words_ids`` ban tokens by the row's history (``ops.constrain`` states the rule: the HF
+        logits processors of the same names) in all three modes and on every path: one kernel launch
+        per step inside the graph or the eager loop on the GPU, the reference on the CPU.  Beam
+        search masks after the log-softmax, as the library does.  At their defaults nothing is
+        launched and the captures and their keys are what they were; otherwise the frozen rule
+        joins the key."""
         if use_graph is None:
             use_graph = input_ids.is_cuda and os.environ.get("CLOUDTIK_AMD_T5_GRAPH", "1") == "1"
         beam_ops.check_beam_args(num_beams, self.cfg.vocab_size, early_stopping)
         sample_ops.check_sample_args(temperature, top_k, top_p, repetition_penalty, num_return_sequences, seed)
+        cons = constrain_ops.check_constrain_args(no_repeat_ngram_size, min_new_tokens, min_length, bad_words_ids,
+                                                  self.cfg.vocab_size, self.cfg.eos_token_id, num_beams, max_new_tokens)
         N = num_return_sequences
         if do_sample:
             if num_beams != 1:
@@ -336,9 +385,9 @@ class T5ForConditionalGeneration(nn.Module):
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
             if use_graph and input_ids.is_cuda:
                 return self._generate_sample_static(input_ids, attention_mask, max_new_tokens, N, seed, temperature,
-                                                    top_k, top_p, repetition_penalty)
+                                                    top_k, top_p, repetition_penalty, cons=cons)
             return self._generate_sample_eager(input_ids, attention_mask, max_new_tokens, N, seed, temperature,
-                                               top_k, top_p, repetition_penalty)
+                                               top_k, top_p, repetition_penalty, cons=cons)
         if temperature != 1.0 or top_k != 0 or top_p != 1.0 or repetition_penalty != 1.0 or seed is not None:
             raise ValueError("temperature, top_k, top_p, repetition_penalty and seed belong to sampling (do_sample=True)")
         if N > num_beams:
@@ -346,16 +395,16 @@ class T5ForConditionalGeneration(nn.Module):
         if num_beams > 1:
             if use_graph and input_ids.is_cuda and trace is None:
                 seq, score = self._generate_beam_static(input_ids, attention_mask, max_new_tokens, num_beams,
-                                                        length_penalty, early_stopping, num_return=N)
+                                                        length_penalty, early_stopping, num_return=N, cons=cons)
             else:
                 seq, score = self._generate_beam_eager(input_ids, attention_mask, max_new_tokens, num_beams,
-                                                       length_penalty, early_stopping, trace, num_return=N)
+                                                       length_penalty, early_stopping, trace, num_return=N, cons=cons)
             return (seq, score) if return_scores else seq
         if return_scores or trace is not None:
             raise ValueError("return_scores and trace belong to beam search (num_beams > 1)")
         if use_graph and input_ids.is_cuda:
             try:
-                return self._generate_graph(input_ids, attention_mask, max_new_tokens)
+                return self._generate_graph(input_ids, attention_mask, max_new_tokens, cons)
             except RuntimeError as e:          # capture unsupported by some op: eager fallback
                 logger.warning("T5 graph decoding unavailable (%s); decoding eagerly", e)
         enc, _ = self.encoder(input_ids, attention_mask)
@@ -363,31 +412,46 @@ class T5ForConditionalGeneration(nn.Module):
         cur = torch.full((B, 1), self.cfg.decoder_start_token_id, dtype=torch.long, device=input_ids.device)
         out, caches = [], None
         done = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
+        con, hist = self._constrainer(cons, input_ids.device), None
+        if con is not None:                    # the row's history as the ban rule reads it: pad after EOS
+            hist = torch.full((B, max_new_tokens), self.cfg.pad_token_id, dtype=torch.long, device=input_ids.device)
         for step in range(max_new_tokens):
             dec, caches = self.decoder(cur, enc=enc, enc_mask=attention_mask, caches=caches, offset=step)
-            nxt = self.logits(dec[:, -1]).float().argmax(-1)
+            logits = self.logits(dec[:, -1])
+            if con is not None:
+                logits = con(logits, hist, torch.tensor([step], dtype=torch.long, device=input_ids.device))
+            nxt = logits.float().argmax(-1)
             nxt = torch.where(done, torch.full_like(nxt, self.cfg.pad_token_id), nxt)
+            if con is not None:
+                hist[:, step] = nxt
             out.append(nxt)
             done |= nxt == self.cfg.eos_token_id
             cur = nxt[:, None]
         return torch.stack(out, 1)
 
-    def _generate_graph(self, input_ids, attention_mask, max_new: int) -> torch.Tensor:
+    def _constrainer(self, cons, dev):
+        """The frozen ban rule of ``generate`` bound to this model's tokens and a device, or None."""
+        if cons is None:
+            return None
+        return constrain_ops.Constrainer(cons, self.cfg.decoder_start_token_id, self.cfg.eos_token_id, dev)
+
+    def _generate_graph(self, input_ids, attention_mask, max_new: int, cons=None) -> torch.Tensor:
         """Graph-replayed greedy decoding.  The captured graph and its static buffers are cached
-        per (batch, source length, steps, masked): a later call only runs the encoder, copies the
-        cross-attention K/V and the source mask into the static buffers and replays."""
+        per (batch, source length, steps, masked) and, when one is on, the ban rule ``cons``: a later
+        call only runs the encoder, copies the cross-attention K/V and the source mask into the
+        static buffers and replays."""
         cfg = self.cfg
         dev = input_ids.device
         B, S, T = input_ids.shape[0], input_ids.shape[1], max_new
         dec = self.decoder
         enc, _ = self.encoder(input_ids, attention_mask)
-        key = (B, S, T, attention_mask is not None, str(dev))
+        key = (B, S, T, attention_mask is not None, str(dev)) + ((cons,) if cons is not None else ())
         cache = getattr(self, "_graphs", None)
         if cache is None:
             cache = self._graphs = {}
         st = cache.get(key)
         if st is None:
-            st = cache[key] = self._capture_decode(B, S, T, enc.dtype, dev, attention_mask is not None)
+            st = cache[key] = self._capture_decode(B, S, T, enc.dtype, dev, attention_mask is not None, cons)
         for i, b in enumerate(dec.blocks):
             st["cross"][i][0].copy_(b.ca._split(b.ca.k(enc)))
             st["cross"][i][1].copy_(b.ca._split(b.ca.v(enc)))
@@ -426,7 +490,7 @@ class T5ForConditionalGeneration(nn.Module):
             x = x + blk.ff(blk.ln_ff(x))
         return dec.final(x)
 
-    def _capture_decode(self, B, S, T, dtype, dev, masked: bool):
+    def _capture_decode(self, B, S, T, dtype, dev, masked: bool, cons=None):
         cfg = self.cfg
         H, D = cfg.num_heads, cfg.d_kv
         dec = self.decoder
@@ -441,10 +505,14 @@ class T5ForConditionalGeneration(nn.Module):
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         slots = torch.arange(T, device=dev)
         pad = torch.full((B,), cfg.pad_token_id, dtype=torch.long, device=dev)
+        con = self._constrainer(cons, dev)         # holds the bad-word tables the captured kernel reads
 
         def step():
             x = self._decode_step_static(cur, pos, slots, kc, vc, cross, enc_bias)
-            nxt = self.logits(x[:, -1]).float().argmax(-1)
+            logits = self.logits(x[:, -1])
+            if con is not None:                    # `out` is the history: slots < pos, pad after EOS
+                con(logits, out, pos)
+            nxt = logits.float().argmax(-1)
             nxt = torch.where(done, pad, nxt)
             out.index_copy_(1, pos, nxt[:, None])
             done.logical_or_(nxt == cfg.eos_token_id)
@@ -472,7 +540,7 @@ class T5ForConditionalGeneration(nn.Module):
     # ------------------------------------------------------------------------- beam search
     @torch.no_grad()
     def _generate_beam_eager(self, input_ids, attention_mask, max_new, K, length_penalty, early_stopping, trace=None,
-                             num_return: int = 1):
+                             num_return: int = 1, cons=None):
         """The reference beam loop, any device and dtype: the growing-cache decoder at batch
         B * K and ``beam_step_reference`` / ``cache_reorder_reference`` after every step."""
         cfg, dev = self.cfg, input_ids.device
@@ -484,10 +552,15 @@ class T5ForConditionalGeneration(nn.Module):
         len_pen = beam_ops.length_penalty_table(T, length_penalty, dev)
         cur = torch.full((B * K, 1), cfg.decoder_start_token_id, dtype=torch.long, device=dev)
         caches = None
+        con = self._constrainer(cons, dev)
         for t in range(T):
             dec, caches = self.decoder(cur, enc=enc, enc_mask=mask, caches=caches, offset=t)
+            logits, ban = self.logits(dec[:, -1]), None
+            if con is not None:                    # row b * K + k has the history run_seq[b, k]
+                ban = con.ban_mask(logits, state["run_seq"].reshape(B * K, T),
+                                   torch.tensor([t], dtype=torch.long, device=dev))
             state, beam_idx, nxt, cand, _ = beam_ops.beam_step_reference(
-                self.logits(dec[:, -1]), state, t, len_pen, cfg.eos_token_id, early_stopping)
+                logits, state, t, len_pen, cfg.eos_token_id, early_stopping, ban=ban)
             if trace is not None:
                 trace.append(cand)
             for c in caches:                       # cross K/V are the same for every beam of an item
@@ -507,12 +580,13 @@ class T5ForConditionalGeneration(nn.Module):
     @torch.no_grad()
     def _generate_beam_static(self, input_ids, attention_mask, max_new, K, length_penalty=1.0, early_stopping=False,
                               fused: bool = True, graph: bool = True, trace=None, select: str = "sort",
-                              num_return: int = 1):
+                              num_return: int = 1, cons=None):
         """Beam search over the static-cache decode step at batch B * K.  ``fused``: the beam
         kernels do the bookkeeping (else the PyTorch reference does, on the same step, so both
         see the same logits); ``graph``: two captured graphs, one per cache parity, are replayed
         in turn (else the same step runs eagerly and fills ``trace``).  Captures are cached like
-        the greedy ones, additionally by (K, length_penalty, early_stopping)."""
+        the greedy ones, additionally by (K, length_penalty, early_stopping) and, when one is on, the
+        ban rule ``cons``."""
         dev = input_ids.device
         B, S, T = input_ids.shape[0], input_ids.shape[1], max_new
         if trace is not None and graph:
@@ -520,13 +594,15 @@ class T5ForConditionalGeneration(nn.Module):
         enc, _ = self.encoder(input_ids, attention_mask)
         masked = attention_mask is not None
         key = ("beam", B, S, T, masked, str(dev), K, float(length_penalty), bool(early_stopping), fused, graph, select)
+        if cons is not None:
+            key = key + (cons,)
         cache = getattr(self, "_graphs", None)
         if cache is None:
             cache = self._graphs = {}
         st = cache.get(key)
         if st is None:
             st = cache[key] = self._capture_beam_decode(B, S, T, enc.dtype, dev, masked, K, length_penalty,
-                                                        early_stopping, fused, graph, select)
+                                                        early_stopping, fused, graph, select, cons)
         for i, b in enumerate(self.decoder.blocks):     # cross K/V: expanded to B * K rows once per call
             st["cross"][i][0].copy_(b.ca._split(b.ca.k(enc)).repeat_interleave(K, 0))
             st["cross"][i][1].copy_(b.ca._split(b.ca.v(enc)).repeat_interleave(K, 0))
@@ -540,7 +616,7 @@ class T5ForConditionalGeneration(nn.Module):
         return self._best_finished(st["state"], num_return)
 
     def _capture_beam_decode(self, B, S, T, dtype, dev, masked, K, length_penalty, early_stopping, fused, graph,
-                             select):
+                             select, cons=None):
         cfg = self.cfg
         H, D, R = cfg.num_heads, cfg.d_kv, B * K
         n = len(self.decoder.blocks)
@@ -563,16 +639,23 @@ class T5ForConditionalGeneration(nn.Module):
         len_pen = beam_ops.length_penalty_table(T, length_penalty, dev)
         reorder = [beam_ops.CacheReorder(kc[p] + vc[p], kc[1 - p] + vc[1 - p]) for p in range(2)] if fused else None
         trace = [None]
+        con = self._constrainer(cons, dev)         # holds the bad-word tables the captured kernel reads
+        hist = state["run_seq"].view(R, T)         # row b * K + k: gathered by source beam in every update
+        ban_lse = torch.empty(R, dtype=torch.float32, device=dev) if con is not None and fused else None
 
         def step(p):
             x = self._decode_step_static(cur, pos, slots, kc[p], vc[p], cross, enc_bias)
             logits = self.logits(x[:, -1])
             if fused:
-                beam_ops.beam_step(logits, state, pos, arrive, len_pen, beam_idx, cur, cfg.eos_token_id, early_stopping)
+                if con is not None:
+                    con(logits, hist, pos, ban_lse)
+                beam_ops.beam_step(logits, state, pos, arrive, len_pen, beam_idx, cur, cfg.eos_token_id, early_stopping,
+                                   ban_lse=ban_lse)
                 reorder[p](beam_idx, pos)
                 return
+            ban = con.ban_mask(logits, hist, pos) if con is not None else None
             new, src, nxt, cand, _ = beam_ops.beam_step_reference(logits, state, pos, len_pen, cfg.eos_token_id,
-                                                                  early_stopping, select=select)
+                                                                  early_stopping, select=select, ban=ban)
             if trace[0] is not None:
                 trace[0].append(cand)
             for name, v in new.items():
@@ -609,7 +692,7 @@ class T5ForConditionalGeneration(nn.Module):
     # ---------------------------------------------------------------------------- sampling
     @torch.no_grad()
     def _generate_sample_eager(self, input_ids, attention_mask, max_new, N, seed, temperature=1.0, top_k=0, top_p=1.0,
-                               repetition_penalty=1.0):
+                               repetition_penalty=1.0, cons=None):
         """The eager sampling loop, any device and dtype: the growing-cache decoder at batch B * N,
         and after every step ``sample_step_reference`` on the CPU or the sampling kernel on the GPU."""
         cfg, dev = self.cfg, input_ids.device
@@ -625,9 +708,12 @@ class T5ForConditionalGeneration(nn.Module):
         rule = (cfg.decoder_start_token_id, cfg.eos_token_id, cfg.pad_token_id, temperature, top_k, top_p,
                 repetition_penalty)
         caches = None
+        con = self._constrainer(cons, dev)
         for t in range(T):
             dec, caches = self.decoder(cur, enc=enc, enc_mask=mask, caches=caches, offset=t)
             logits = self.logits(dec[:, -1])
+            if con is not None:                    # the bans first: `out` is the history
+                logits = con(logits.contiguous(), out, pos)
             if dev.type == "cuda":
                 sample_ops.sample_step(logits.contiguous(), out, done, cur, pos, seed_t, *rule)
             else:
@@ -636,26 +722,27 @@ class T5ForConditionalGeneration(nn.Module):
 
     @torch.no_grad()
     def _generate_sample_static(self, input_ids, attention_mask, max_new, N, seed, temperature=1.0, top_k=0,
-                                top_p=1.0, repetition_penalty=1.0, graph: bool = True):
+                                top_p=1.0, repetition_penalty=1.0, graph: bool = True, cons=None):
         """Sampling over the static-cache decode step at batch R = B * N, ended by the sampling
         kernel.  ``graph``: the captured step is replayed (else the same step runs eagerly).
         Captures are cached like the greedy ones, additionally by the sampling parameters, which
-        are launch arguments; the seed is a device tensor ``reset`` rewrites, so it is not in the
-        key."""
+        are launch arguments, and, when one is on, the ban rule ``cons``; the seed is a device tensor
+        ``reset`` rewrites, so it is not in the key."""
         dev = input_ids.device
         B, S, T = input_ids.shape[0], input_ids.shape[1], max_new
         R = B * N
         enc, _ = self.encoder(input_ids, attention_mask)
         masked = attention_mask is not None
         key = ("sample", R, S, T, masked, str(dev), float(temperature), int(top_k), float(top_p),
-               float(repetition_penalty), graph)
+               float(repetition_penalty)) + ((cons,) if cons is not None else ()) + (graph,)
         cache = getattr(self, "_graphs", None)
         if cache is None:
             cache = self._graphs = {}
         st = cache.get(key)
         if st is None:
             st = cache[key] = self._capture_sample_decode(R, S, T, enc.dtype, dev, masked, float(temperature),
-                                                          int(top_k), float(top_p), float(repetition_penalty), graph)
+                                                          int(top_k), float(top_p), float(repetition_penalty), graph,
+                                                          cons)
         for i, b in enumerate(self.decoder.blocks):     # cross K/V: expanded to B * N rows once per call
             st["cross"][i][0].copy_(b.ca._split(b.ca.k(enc)).repeat_interleave(N, 0))
             st["cross"][i][1].copy_(b.ca._split(b.ca.v(enc)).repeat_interleave(N, 0))
@@ -667,7 +754,7 @@ class T5ForConditionalGeneration(nn.Module):
         return st["out"].clone()
 
     def _capture_sample_decode(self, R, S, T, dtype, dev, masked, temperature, top_k, top_p, repetition_penalty,
-                               graph):
+                               graph, cons=None):
         cfg = self.cfg
         H, D = cfg.num_heads, cfg.d_kv
         dec = self.decoder
@@ -684,10 +771,14 @@ class T5ForConditionalGeneration(nn.Module):
         slots = torch.arange(T, device=dev)
         rule = (cfg.decoder_start_token_id, cfg.eos_token_id, cfg.pad_token_id, temperature, top_k, top_p,
                 repetition_penalty)
+        con = self._constrainer(cons, dev)         # holds the bad-word tables the captured kernel reads
 
         def step():
             x = self._decode_step_static(cur, pos, slots, kc, vc, cross, enc_bias)
-            sample_ops.sample_step(self.logits(x[:, -1]), out, done, cur, pos, seed, *rule)
+            logits = self.logits(x[:, -1])
+            if con is not None:                    # the bans first: `out` is the history
+                con(logits, out, pos)
+            sample_ops.sample_step(logits, out, done, cur, pos, seed, *rule)
 
         def reset(seed_value=0):
             seed.fill_(seed_value)

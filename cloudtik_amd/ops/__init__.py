@@ -134,3 +134,5 @@ from . import beam  # noqa: E402,F401
 from .beam import beam_step, beam_step_reference, beam_topk, cache_reorder_reference  # noqa: E402,F401
 from . import sampling  # noqa: E402,F401
 from .sampling import sample_step, sample_step_reference  # noqa: E402,F401
+from . import constrain  # noqa: E402,F401
+from .constrain import constrain_reference, logits_constrain  # noqa: E402,F401

@@ -86,13 +86,14 @@ def length_penalty_table(steps: int, length_penalty: float, device=None) -> torc
 
 
 def beam_step_reference(logits: torch.Tensor, state: State, t: Union[int, torch.Tensor], len_pen: torch.Tensor,
-                        eos: int, early_stopping: bool = False, select: str = "sort"
-                        ) -> Tuple[State, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                        eos: int, early_stopping: bool = False, select: str = "sort",
+                        ban: Optional[torch.Tensor] = None) -> Tuple[State, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """One step of the rules above.  Returns (new state, beam_idx [B * K] with the batch offset
     b * K added, next_tok [B * K], cand_score [B, 2K], cand_idx [B, 2K]); ``state`` is left as it
     is.  ``t`` may be a device tensor (nothing here reads it back).  ``select="topk"`` takes the
     2K candidates with ``torch.topk``, which is faster and leaves a tie across rank 2K to the
-    library; "sort" is the rule."""
+    library; "sort" is the rule.  ``ban`` bool [B * K, V] (``ops/constrain.py``) sets the candidates of
+    banned tokens to -inf after the log-softmax, which still normalises over the whole row."""
     run_seq, run_score = state["run_seq"], state["run_score"]
     fin_seq, fin_score, fin_flag, unsat = state["fin_seq"], state["fin_score"], state["fin_flag"], state["unsat"]
     B, K, T = run_seq.shape
@@ -103,7 +104,10 @@ def beam_step_reference(logits: torch.Tensor, state: State, t: Union[int, torch.
     at_t = torch.arange(T, device=dev) == t                                           # [T]
     L = len_pen.to(dev).index_select(0, t.reshape(1)).reshape(())       # no host read: t may live on the device
 
-    flat = (torch.log_softmax(logits.float(), -1).view(B, K, V) + run_score[:, :, None]).view(B, K * V)
+    logp = torch.log_softmax(logits.float(), -1)
+    if ban is not None:
+        logp = logp.masked_fill(ban, float("-inf"))
+    flat = (logp.view(B, K, V) + run_score[:, :, None]).view(B, K * V)
     if select == "topk":
         s, idx = torch.topk(flat, 2 * K, dim=1)
         idx, o = torch.sort(idx, dim=1)                                               # ties inside the set
@@ -171,16 +175,21 @@ def beam_topk(logits: torch.Tensor, num_beams: int):
 
 
 def beam_step(logits: torch.Tensor, state: State, pos: torch.Tensor, arrive: torch.Tensor, len_pen: torch.Tensor,
-              beam_idx: torch.Tensor, cur: torch.Tensor, eos: int, early_stopping: bool = False):
+              beam_idx: torch.Tensor, cur: torch.Tensor, eos: int, early_stopping: bool = False,
+              ban_lse: Optional[torch.Tensor] = None):
     """The fused form of ``beam_step_reference`` on the GPU, in place: reads step ``pos[0]``,
     rewrites ``state``, ``beam_idx`` [B * K] and the decoder's next input ``cur`` [B * K, 1], and
     advances ``pos``.  ``arrive`` is an int32 [1] zero the kernel uses to find its last workgroup.
-    Returns the step's candidates (cand_score [B, 2K], cand_idx [B, 2K])."""
+    Returns the step's candidates (cand_score [B, 2K], cand_idx [B, 2K]).  With ``ban_lse`` fp32
+    [B * K], ``logits`` are rows masked by ``ops.constrain.logits_constrain`` and ``ban_lse`` the
+    log-sum-exp of what it masked: the whole row's log-sum-exp is restored from the two."""
     if not _pkg()._use_native(logits):
         raise RuntimeError("beam_step is a GPU kernel; use beam_step_reference on the CPU")
     C = _pkg().require_native()
     K = state["run_seq"].shape[1]
     lse, val, tok = C.beam_topk(logits.contiguous(), K)
+    if ban_lse is not None:
+        lse = torch.logaddexp(lse, ban_lse)
     return C.beam_update(lse, val, tok, state["run_seq"], state["run_score"], state["fin_seq"], state["fin_score"],
                          state["fin_flag"], state["unsat"], len_pen, pos, arrive, beam_idx, cur,
                          int(logits.shape[-1]), int(eos), bool(early_stopping))

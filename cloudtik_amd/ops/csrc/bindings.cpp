@@ -858,6 +858,7 @@ void register_conv(pybind11::module& m);   // bindings_conv.cpp
 void register_quant(pybind11::module& m);  // bindings_quant.cpp
 void register_beam(pybind11::module& m);   // bindings_beam.cpp
 void register_sampling(pybind11::module& m); // bindings_sampling.cpp
+void register_constrain(pybind11::module& m); // bindings_constrain.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "cloudtik_amd CDNA4 (gfx950) op library";
@@ -870,6 +871,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_quant(m);
   register_beam(m);
   register_sampling(m);
+  register_constrain(m);
   m.def("maxpool3s2_bwd_bn", &maxpool3s2_bwd_bn);
   m.def("bn_fwd_train_given2", &bn_fwd_train_given2);
   m.def("bn_bwd_given_pair", &bn_bwd_given_pair);

@@ -5,6 +5,12 @@
     python examples/ai/t5_generate.py --checkpoint /models/t5-small --text "translate English to German: Hello"
     python examples/ai/t5_generate.py --num-beams 4 --length-penalty 0.6 --early-stopping
     python examples/ai/t5_generate.py --do-sample --top-k 50 --top-p 0.95 --temperature 0.8 --num-return-sequences 3 --seed 7
+    python examples/ai/t5_generate.py --no-repeat-ngram-size 3 --min-length 8 --bad-words 5 --bad-words 17,42
+    python examples/ai/t5_generate.py --checkpoint /models/t5-small --task summarization --text "..."
+
+``--task`` takes the generation settings the checkpoint's ``config.json`` ships for that task
+(``task_specific_params``: beams, length penalty, minimum length, n-gram ban, ...) and puts the
+task's prefix in front of every ``--text``; flags given on the command line are overridden by it.
 
 ``--checkpoint`` is a directory holding ``config.json`` and ``model.safetensors`` or
 ``pytorch_model.bin`` (nothing is downloaded).  With a ``spiece.model`` in it and the
@@ -62,32 +68,51 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--num-return-sequences", type=int, default=1, help="samples per source")
     ap.add_argument("--seed", type=int, default=None, help="sampling seed (default: from torch's generator)")
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=0, help="no n-gram of this size twice (0: off)")
+    ap.add_argument("--min-new-tokens", type=int, default=0, help="no EOS before this many new tokens")
+    ap.add_argument("--min-length", type=int, default=0, help="the same, counting the start token as the library does")
+    ap.add_argument("--bad-words", action="append", default=None, metavar="ID[,ID...]",
+                    help="token ids of a sequence that must not appear (repeatable)")
+    ap.add_argument("--task", default=None, help="use the checkpoint's task_specific_params of this task")
     a = ap.parse_args()
 
     gpu = torch.cuda.is_available()
     device = torch.device("cuda", 0) if gpu else torch.device("cpu")
     model = load_model(a.checkpoint, a.size, device, torch.bfloat16 if gpu else torch.float32)
     tok = load_tokenizer(a.checkpoint)
+    beam_kw = dict(max_new_tokens=a.max_new_tokens, num_beams=a.num_beams, length_penalty=a.length_penalty,
+                   early_stopping=a.early_stopping)
+    ban_kw = dict(no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens, min_length=a.min_length,
+                  bad_words_ids=[[int(v) for v in w.split(",")] for w in a.bad_words] if a.bad_words else None)
+    prefix = ""
+    if a.task is not None:
+        if a.checkpoint is None:
+            ap.error("--task needs --checkpoint (the settings come from its config.json)")
+        from cloudtik_amd.models.t5 import generate_kwargs_for_task
+        task_kw, prefix = generate_kwargs_for_task(os.path.join(a.checkpoint, "config.json"), a.task)
+        for name, value in task_kw.items():
+            (ban_kw if name in ban_kw else beam_kw)[name] = value
+        print(f"task {a.task}: {task_kw}, prefix {prefix!r}")
     if tok is not None and a.text:
-        enc = tok(a.text, return_tensors="pt", padding=True)
+        enc = tok([prefix + t for t in a.text], return_tensors="pt", padding=True)
         ids, mask = enc["input_ids"].to(device), enc["attention_mask"].to(device)
     else:
         g = torch.Generator().manual_seed(0)
         ids = torch.randint(2, model.cfg.vocab_size, (a.batch, a.source_len), generator=g).to(device)
         mask = torch.ones_like(ids)
 
-    greedy = model.generate(ids, mask, max_new_tokens=a.max_new_tokens)
-    beam, score = model.generate(ids, mask, max_new_tokens=a.max_new_tokens, num_beams=a.num_beams,
-                                 length_penalty=a.length_penalty, early_stopping=a.early_stopping, return_scores=True)
+    steps, beams = beam_kw["max_new_tokens"], beam_kw["num_beams"]
+    greedy = model.generate(ids, mask, max_new_tokens=steps, **ban_kw)
+    beam, score = model.generate(ids, mask, return_scores=True, **beam_kw, **ban_kw)
     show = (lambda row: tok.decode(row, skip_special_tokens=True)) if tok is not None else (lambda row: row.tolist())
     for i in range(ids.shape[0]):
         print(f"[{i}] greedy: {show(greedy[i])}")
-        print(f"[{i}] beam {a.num_beams} (score {float(score[i]):.4f}): {show(beam[i])}")
+        print(f"[{i}] beam {beams} (score {float(score[i]):.4f}): {show(beam[i])}")
     if a.do_sample:
         n = a.num_return_sequences
-        samples = model.generate(ids, mask, max_new_tokens=a.max_new_tokens, do_sample=True, temperature=a.temperature,
+        samples = model.generate(ids, mask, max_new_tokens=steps, do_sample=True, temperature=a.temperature,
                                  top_k=a.top_k, top_p=a.top_p, repetition_penalty=a.repetition_penalty,
-                                 num_return_sequences=n, seed=a.seed)
+                                 num_return_sequences=n, seed=a.seed, **ban_kw)
         for i in range(ids.shape[0]):
             for j in range(n):                     # rows i * n .. i * n + n - 1 belong to source i
                 print(f"[{i}] sample {j}: {show(samples[i * n + j])}")
