@@ -321,6 +321,13 @@ class T5ForConditionalGeneration(nn.Module):
     def logits(self, dec):
         return F.linear(dec * (self.cfg.d_model ** -0.5), self.shared.weight)
 
+    def quantize_dynamic(self):
+        """The int8 inference model of this one (``models.t5_quant``; the reference's
+        ``torch.quantization.quantize_dynamic`` step): every linear and the output head in int8,
+        ``generate`` with all its modes unchanged.  This model is left as it is."""
+        from cloudtik_amd.models.t5_quant import QuantT5ForConditionalGeneration
+        return QuantT5ForConditionalGeneration.from_float(self)
+
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 32,
                  use_graph: Optional[bool] = None, num_beams: int = 1, length_penalty: float = 1.0,

@@ -129,7 +129,7 @@ from .deform import (DeformConv, DeformRoIPooling, DeformRoIPoolingPack, Modulat
                      ModulatedDeformConvPack, deform_conv2d, deform_roi_pooling)
 from .rnnt import rnnt_loss, rnnt_loss_reference  # noqa: E402,F401
 from .quant import (conv2d_i8_static, fold_bn, layer_norm_quant, linear_i8, linear_i8_static,  # noqa: E402,F401
-                    quantize_rows, quantize_static, quantize_weight)
+                    quantize_rows, quantize_static, quantize_weight, rms_norm_quant)
 from . import beam  # noqa: E402,F401
 from .beam import beam_step, beam_step_reference, beam_topk, cache_reorder_reference  # noqa: E402,F401
 from . import sampling  # noqa: E402,F401

@@ -859,6 +859,7 @@ void register_quant(pybind11::module& m);  // bindings_quant.cpp
 void register_beam(pybind11::module& m);   // bindings_beam.cpp
 void register_sampling(pybind11::module& m); // bindings_sampling.cpp
 void register_constrain(pybind11::module& m); // bindings_constrain.cpp
+void register_quant_skinny(pybind11::module& m); // bindings_quant_skinny.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "cloudtik_amd CDNA4 (gfx950) op library";
@@ -872,6 +873,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_beam(m);
   register_sampling(m);
   register_constrain(m);
+  register_quant_skinny(m);
   m.def("maxpool3s2_bwd_bn", &maxpool3s2_bwd_bn);
   m.def("bn_fwd_train_given2", &bn_fwd_train_given2);
   m.def("bn_bwd_given_pair", &bn_bwd_given_pair);

@@ -11,18 +11,25 @@ same rule against one calibrated range per tensor, so the cast is elementwise an
 the kernel that produces the tensor.  ``conv2d_i8_static`` (csrc/quant_conv.hip) is the static int8
 convolution, with BatchNorm folded into its weights and bias (``fold_bn``).
 
+Decoding (csrc/quant_skinny.hip): ``linear_i8`` with up to ``SKINNY_MAX_M`` rows runs in a one-launch
+weight-streaming kernel whose epilogue also carries a ReLU or a residual add, and ``rms_norm_quant``
+is the RMS norm that emits the int8 rows and scales of the linear behind it.
+
 GPU tensors go to the HIP kernels (required; shapes outside their tiling raise), CPU tensors
 to ``ops.reference``.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple, Union
 
 import torch
 
 from . import reference as ref
 
-ACT_NONE, ACT_GELU = ref.ACT_NONE, ref.ACT_GELU
+ACT_NONE, ACT_GELU, ACT_RELU = ref.ACT_NONE, ref.ACT_GELU, ref.ACT_RELU
+
+SKINNY_MAX_M = 64         # rows the decode GEMM (csrc/quant_skinny.hip) takes
 
 Quantized = Tuple[torch.Tensor, torch.Tensor]
 
@@ -52,16 +59,37 @@ def quantize_weight(w: torch.Tensor) -> Quantized:
     return q.contiguous().to(w.device), s.contiguous().to(w.device)
 
 
+def skinny_enabled() -> bool:
+    """``CLOUDTIK_AMD_I8_SKINNY=0`` sends every ``linear_i8`` to the tiled kernel (A/B runs)."""
+    return os.environ.get("CLOUDTIK_AMD_I8_SKINNY", "1") != "0"
+
+
 def linear_i8(x: Union[torch.Tensor, Quantized], w_q: torch.Tensor, w_scale: torch.Tensor,
               bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
-              dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-    """act(x @ dequant(w_q)^T + bias) with int8 operands and exact int32 accumulation.
+              dtype: Optional[torch.dtype] = None, residual: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(x @ dequant(w_q)^T + bias) (+ residual) with int8 operands and exact int32 accumulation.
 
     ``x`` is a floating tensor [..., K] (quantized per row here) or the ``(q, scale)`` pair
     ``quantize_rows`` returned.  ``dtype`` is the output type; it defaults to the input's type
-    (a quantized pair: bf16 on the GPU, fp32 on the CPU)."""
-    if act not in (ACT_NONE, ACT_GELU):
-        raise ValueError(f"linear_i8: act must be ACT_NONE or ACT_GELU, got {act}")
+    (a quantized pair: bf16 on the GPU, fp32 on the CPU).  ``act`` is ACT_NONE, ACT_GELU or
+    ACT_RELU.  ``residual`` [..., N] of the output type is added to the ROUNDED result
+    (``reference.dequant_epilogue`` states the rule), so the call equals the linear followed by
+    ``residual + h``; it does not combine with ACT_RELU.  ACT_RELU is the bias-free epilogue T5's
+    feed-forward needs: together with a ``bias`` it raises, as every ReLU call did before this
+    activation existed here (``reference.dequant_epilogue`` and the kernel take both).  ``out``
+    (GPU) receives the result and may be the residual itself.
+
+    On the GPU up to ``SKINNY_MAX_M`` rows without a bias, with ACT_NONE / ACT_RELU, run in the
+    one-launch decode kernel, epilogue included; everything else (more rows, GELU, and calls with
+    a bias: the classifier's, which keep the kernel they had) runs in the tiled kernel, with ReLU
+    and the residual applied by PyTorch ops after it."""
+    if act not in (ACT_NONE, ACT_GELU, ACT_RELU):
+        raise ValueError(f"linear_i8: act must be ACT_NONE, ACT_GELU or ACT_RELU, got {act}")
+    if act == ACT_RELU and residual is not None:
+        raise ValueError("linear_i8: ACT_RELU together with a residual is not supported")
+    if act == ACT_RELU and bias is not None:
+        raise ValueError("linear_i8: ACT_RELU together with a bias is not supported")
     if isinstance(x, torch.Tensor):
         if dtype is None:
             dtype = x.dtype
@@ -72,14 +100,58 @@ def linear_i8(x: Union[torch.Tensor, Quantized], w_q: torch.Tensor, w_scale: tor
     K = a_q.shape[-1]
     N = w_q.shape[0]
     a2, s1 = a_q.reshape(-1, K), a_s.reshape(-1)
+    r2 = None
+    if residual is not None:
+        if residual.shape != (*lead, N):
+            raise ValueError(f"linear_i8: the residual must have shape {(*lead, N)}, got {tuple(residual.shape)}")
+        r2 = residual.reshape(-1, N)
     if _pkg()._use_native(a_q, w_q):
         if dtype not in (None, torch.bfloat16):
             raise TypeError(f"linear_i8: the GPU kernel writes bf16, not {dtype}")
-        out = torch.empty(a2.shape[0], N, device=a_q.device, dtype=torch.bfloat16)
-        _pkg().require_native().gemm_i8_nt(a2.contiguous(), s1.contiguous(), w_q, w_scale, bias, int(act), out)
+        M = a2.shape[0]
+        if out is None:
+            o2 = torch.empty(M, N, device=a_q.device, dtype=torch.bfloat16)
+        else:
+            if out.shape != (*lead, N) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+                raise ValueError(f"linear_i8: out must be a contiguous bf16 tensor of shape {(*lead, N)}")
+            o2 = out.view(M, N)
+        C = _pkg().require_native()
+        if M <= SKINNY_MAX_M and bias is None and act != ACT_GELU and skinny_enabled():
+            C.gemm_i8_skinny(a2.contiguous(), s1.contiguous(), w_q, w_scale, bias, int(act),
+                             r2.contiguous() if r2 is not None else None, o2)
+        else:
+            # the tiled kernel has no ReLU / residual epilogue: the same arithmetic as PyTorch ops
+            # (ReLU commutes with the rounding; the bf16 add rounds the sum of the rounded result)
+            tiled = o2 if r2 is None else torch.empty_like(o2)
+            C.gemm_i8_nt(a2.contiguous(), s1.contiguous(), w_q, w_scale, bias,
+                         int(ACT_GELU if act == ACT_GELU else ACT_NONE), tiled)
+            if act == ACT_RELU:
+                torch.relu_(tiled)
+            if r2 is not None:
+                torch.add(tiled, r2, out=o2)
+        res = o2
     else:
-        out = ref.linear_i8(a2, s1, w_q, w_scale, bias, act, dtype or torch.float32)
-    return out.view(*lead, N)
+        if out is not None:
+            raise ValueError("linear_i8: out belongs to the GPU path")
+        res = ref.linear_i8(a2, s1, w_q, w_scale, bias, act, dtype or torch.float32, r2)
+    return res.view(*lead, N)
+
+
+def rms_norm_quant(x: torch.Tensor, gamma: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None,
+                   emit_y: bool = True) -> Tuple[Optional[torch.Tensor], Quantized]:
+    """RMS norm that also emits its output quantized per row: ``(y, (q, scale))`` with
+    y = RMSNorm(x + residual) * gamma exactly what ``ops.layer_norm(..., rms=True)`` returns and
+    ``(q, scale) = quantize_rows(y)``, computed from the rounded y.  One kernel on the GPU (bf16,
+    last dimension a multiple of 16 up to 2048); ``emit_y=False`` skips writing y there and
+    returns None for it (the consumer is an int8 linear alone)."""
+    if _pkg()._use_native(x):
+        if x.dtype != torch.bfloat16:
+            raise TypeError(f"rms_norm_quant: GPU input must be bf16, got {x.dtype}")
+        y, q, s = _pkg().require_native().rmsnorm_quant_rows(
+            x.contiguous(), residual.contiguous() if residual is not None else None, gamma, float(eps), bool(emit_y))
+        return y, (q, s)
+    y, qs = ref.rms_norm_quant(x, gamma, eps, residual)
+    return (y if emit_y else None), qs
 
 
 # ------------------------------------------------------------------ static (calibrated) ranges

@@ -182,21 +182,40 @@ def gemm_i8_nt_raw(a_q, w_q):
     return torch.matmul(a_q.to(torch.int32), w_q.to(torch.int32).t())
 
 
-def dequant_epilogue(acc, a_scale, w_scale, bias=None, act=ACT_NONE, dtype=torch.float32):
-    """y = act(acc * (a_scale[m] * w_scale[n]) + bias[n]) in fp32, rounded to ``dtype``."""
+def dequant_epilogue(acc, a_scale, w_scale, bias=None, act=ACT_NONE, dtype=torch.float32, residual=None):
+    """y = act(acc * (a_scale[m] * w_scale[n]) + bias[n]) in fp32, rounded to ``dtype``; with a
+    ``residual`` [M, N] of ``dtype`` then y = round(float(y) + float(residual)) -- rounded BEFORE
+    the add, so the fused op equals the unfused chain (the linear, then ``x + h`` in ``dtype``).
+    ``act`` is ACT_NONE, ACT_GELU or ACT_RELU; ReLU together with a residual raises."""
     y = acc.to(torch.float32) * (a_scale.float().unsqueeze(-1) * w_scale.float().unsqueeze(0))
     if bias is not None:
         y = y + bias.float()
     if act == ACT_GELU:
         y = F.gelu(y)
+    elif act == ACT_RELU:
+        if residual is not None:
+            raise ValueError("linear_i8: ACT_RELU together with a residual is not supported")
+        y = F.relu(y)
     elif act != ACT_NONE:
         raise ValueError(f"linear_i8: unsupported activation {act}")
-    return y.to(dtype)
+    y = y.to(dtype)
+    if residual is not None:
+        if residual.dtype != dtype or residual.shape != y.shape:
+            raise ValueError(f"linear_i8: the residual must be {dtype} of shape {tuple(y.shape)}")
+        y = (y.float() + residual.float()).to(dtype)
+    return y
 
 
-def linear_i8(a_q, a_scale, w_q, w_scale, bias=None, act=ACT_NONE, dtype=torch.float32):
+def linear_i8(a_q, a_scale, w_q, w_scale, bias=None, act=ACT_NONE, dtype=torch.float32, residual=None):
     """a_q [M, K] int8 with per-row scales against w_q [N, K] int8 with per-channel scales."""
-    return dequant_epilogue(gemm_i8_nt_raw(a_q, w_q), a_scale, w_scale, bias, act, dtype)
+    return dequant_epilogue(gemm_i8_nt_raw(a_q, w_q), a_scale, w_scale, bias, act, dtype, residual)
+
+
+def rms_norm_quant(x, gamma, eps, residual=None):
+    """(y, (q, scale)): y = RMSNorm(x + residual) * gamma exactly as ``layer_norm(..., rms=True)``
+    returns it, and ``quantize_rows`` of that ROUNDED y."""
+    y, _ = layer_norm(x, gamma, None, eps, None, residual, rms=True)
+    return y, quantize_rows(y)
 
 
 # ------------------------------------------------------------------ static int8 quantization

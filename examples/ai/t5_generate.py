@@ -7,10 +7,15 @@
     python examples/ai/t5_generate.py --do-sample --top-k 50 --top-p 0.95 --temperature 0.8 --num-return-sequences 3 --seed 7
     python examples/ai/t5_generate.py --no-repeat-ngram-size 3 --min-length 8 --bad-words 5 --bad-words 17,42
     python examples/ai/t5_generate.py --checkpoint /models/t5-small --task summarization --text "..."
+    python examples/ai/t5_generate.py --precision int8                  # every linear and the head in int8
 
 ``--task`` takes the generation settings the checkpoint's ``config.json`` ships for that task
 (``task_specific_params``: beams, length penalty, minimum length, n-gram ban, ...) and puts the
 task's prefix in front of every ``--text``; flags given on the command line are overridden by it.
+
+``--precision int8`` quantizes the loaded model (``T5ForConditionalGeneration.quantize_dynamic``:
+int8 weights with one scale per output channel, activations quantized per token on every call)
+and generates with that; every mode and flag works as on the bf16 model.
 
 ``--checkpoint`` is a directory holding ``config.json`` and ``model.safetensors`` or
 ``pytorch_model.bin`` (nothing is downloaded).  With a ``spiece.model`` in it and the
@@ -74,11 +79,15 @@ def main():
     ap.add_argument("--bad-words", action="append", default=None, metavar="ID[,ID...]",
                     help="token ids of a sequence that must not appear (repeatable)")
     ap.add_argument("--task", default=None, help="use the checkpoint's task_specific_params of this task")
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "int8"],
+                    help="int8: dynamic post-training quantization of every linear and the output head")
     a = ap.parse_args()
 
     gpu = torch.cuda.is_available()
     device = torch.device("cuda", 0) if gpu else torch.device("cpu")
     model = load_model(a.checkpoint, a.size, device, torch.bfloat16 if gpu else torch.float32)
+    if a.precision == "int8":
+        model = model.quantize_dynamic()
     tok = load_tokenizer(a.checkpoint)
     beam_kw = dict(max_new_tokens=a.max_new_tokens, num_beams=a.num_beams, length_penalty=a.length_penalty,
                    early_stopping=a.early_stopping)
