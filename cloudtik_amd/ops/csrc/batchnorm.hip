@@ -65,7 +65,12 @@ __device__ __forceinline__ void bn_thread(const BnLayout& L, int& cv, int& rl) {
   rl = threadIdx.x / L.CV;
 }
 
-// per-block (mean, M2) over rows [b*R, (b+1)*R), 4 rows in flight per thread
+// per-block (mean, M2) over rows [b*R, (b+1)*R), 4 rows in flight per thread.  The squares are
+// summed about a per-channel pivot p, the block's first row: M2 = sum (x - p)^2 - n (mean - p)^2.
+// The plain sum of squares minus sum times mean cancels as |mean| / std grows (relative error of
+// the variance ~ (mean / std)^2 x 2^-24 per rounding); about the pivot both terms are of the
+// size of the variance itself.  The mean stays the plain sum over n: summed about the pivot its
+// partial sums grow with n |mean - p| and it lost digits on centred channels.
 template <int U>
 __global__ __launch_bounds__(BN_RT) void bn_stats_kernel(const bf16_t* __restrict__ x, BnLayout L,
                                                          float* __restrict__ pmean,
@@ -76,9 +81,12 @@ __global__ __launch_bounds__(BN_RT) void bn_stats_kernel(const bf16_t* __restric
   bn_thread(L, cv, rl);
   const int r0 = blockIdx.x * L.rows_per_blk;
   const int r1 = min(L.M, r0 + L.rows_per_blk);
-  float s[8], q[8];
+  float s[8], q[8], p[8];
+  {
+    const u16x8 pv = r0 < r1 ? reinterpret_cast<const u16x8*>(x + (size_t)r0 * L.C)[cv] : u16x8(0);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
+    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; p[j] = bf2f(pv[j]); }
+  }
   if (rl < L.RPI) {
     int r = r0 + rl;
     for (; r + (U - 1) * L.RPI < r1; r += U * L.RPI) {
@@ -88,12 +96,12 @@ __global__ __launch_bounds__(BN_RT) void bn_stats_kernel(const bf16_t* __restric
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const float f = bf2f(v[u][j]); s[j] += f; q[j] += f * f; }
+        for (int j = 0; j < 8; ++j) { const float f = bf2f(v[u][j]), g = f - p[j]; s[j] += f; q[j] += g * g; }
     }
     for (; r < r1; r += L.RPI) {
       const u16x8 v = reinterpret_cast<const u16x8*>(x + (size_t)r * L.C)[cv];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { const float f = bf2f(v[j]); s[j] += f; q[j] += f * f; }
+      for (int j = 0; j < 8; ++j) { const float f = bf2f(v[j]), g = f - p[j]; s[j] += f; q[j] += g * g; }
     }
   }
   bn_block_sum2(s, q, ls, lq, L.RPI, rl, L.CV);
@@ -103,12 +111,18 @@ __global__ __launch_bounds__(BN_RT) void bn_stats_kernel(const bf16_t* __restric
     for (int j = 0; j < 8; ++j) {
       const int c = cv * 8 + j;
       const float mean = n > 0.f ? s[j] / n : 0.f;
+      const float dm = mean - p[j];
       pmean[(size_t)blockIdx.x * L.C + c] = mean;
-      pm2[(size_t)blockIdx.x * L.C + c] = n > 0.f ? fmaxf(q[j] - s[j] * mean, 0.f) : 0.f;
+      pm2[(size_t)blockIdx.x * L.C + c] = n > 0.f ? fmaxf(q[j] - n * dm * dm, 0.f) : 0.f;
     }
   }
 }
 
+
+// gamma / beta element c, read in the parameters' own dtype (pf32: fp32, else bf16)
+__device__ __forceinline__ float bn_param(const void* p, int c, int pf32) {
+  return pf32 ? static_cast<const float*>(p)[c] : bf2f(static_cast<const bf16_t*>(p)[c]);
+}
 
 // Merge of the block partials (per-block mean and M2 over n_b rows); writes save_mean /
 // save_invstd, the affine (a, b) and updates the running statistics.  A 1024-thread block
@@ -121,7 +135,7 @@ __global__ __launch_bounds__(BN_RT) void bn_stats_kernel(const bf16_t* __restric
 // 64 cache lines per load.)
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(
     const float* __restrict__ pmean, const float* __restrict__ pm2, int nblk, BnLayout L,
-    const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, float momentum,
+    const void* __restrict__ gamma, const void* __restrict__ beta, int pf32, float eps, float momentum,
     float* __restrict__ run_mean, float* __restrict__ run_var, float* __restrict__ save_mean,
     float* __restrict__ save_invstd, float* __restrict__ coef_a, float* __restrict__ coef_b) {
   __shared__ float lsum[16][64], lmean[64];
@@ -192,7 +206,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(
   const float n = (float)L.M;
   const float var = fmaxf(q / n, 0.f);
   const float invstd = rsqrtf(var + eps);
-  const float g = gamma ? bf2f(gamma[c]) : 1.f, bt = beta ? bf2f(beta[c]) : 0.f;
+  const float g = gamma ? bn_param(gamma, c, pf32) : 1.f, bt = beta ? bn_param(beta, c, pf32) : 0.f;
   save_mean[c] = mean;
   save_invstd[c] = invstd;
   coef_a[c] = g * invstd;
@@ -414,7 +428,7 @@ __global__ __launch_bounds__(BN_RT) void bn_bwd_reduce_kernel(
 template <typename PT>
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(
     const float* __restrict__ p1, const float* __restrict__ p2, int nblk, int M, int C,
-    const bf16_t* __restrict__ gamma, const float* __restrict__ mean,
+    const PT* __restrict__ gamma, const float* __restrict__ mean,
     const float* __restrict__ invstd, PT* __restrict__ dgamma, PT* __restrict__ dbeta,
     float* __restrict__ ca, float* __restrict__ c1, float* __restrict__ c0, int acc) {
   __shared__ float l1[16][64], l2[16][64];
@@ -436,13 +450,20 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(
   // no separate AccumulateGrad kernel runs per BatchNorm parameter
   if (dgamma) dgamma[c] = from_f<PT>(acc ? to_f<PT>(dgamma[c]) + sdx : sdx);
   if (dbeta) dbeta[c] = from_f<PT>(acc ? to_f<PT>(dbeta[c]) + sdy : sdy);
-  const float g = gamma ? bf2f(gamma[c]) : 1.f;
+  const float g = gamma ? to_f<PT>(gamma[c]) : 1.f;
   const float is = invstd[c];
   const float a = g * is;
   const float k = -a * sdx / M;  // coefficient of xhat
   ca[c] = a;
   c1[c] = k * is;
   c0[c] = -a * sdy / M - k * is * mean[c];
+}
+
+// dx = a dy' + k x + z, evaluated identically by the single and the pair apply kernel (explicit
+// fused multiply-adds: left to the compiler the two kernels contracted differently, and a pair
+// backward differed from the two backwards it replaces in an element per ~10^5)
+__device__ __forceinline__ float bn_dx(float a, float d, float k, float x, float z) {
+  return __builtin_fmaf(a, d, __builtin_fmaf(k, x, z));
 }
 
 template <int BN_EW>
@@ -485,7 +506,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float d = on[j] ? bf2f(g[u][j]) : 0.f;
-        o[j] = f2bf(aa[j] * d + kk[j] * bf2f(xv[u][j]) + zz[j]);
+        o[j] = f2bf(bn_dx(aa[j], d, kk[j], bf2f(xv[u][j]), zz[j]));
         od[j] = f2bf(d);
       }
       reinterpret_cast<u16x8*>(dx)[v] = o;
@@ -758,8 +779,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float d = bf2f(g[j]);
-      o[j] = f2bf(aa[j] * d + kk[j] * bf2f(xv[j]) + zz[j]);
-      o2[j] = f2bf(a2[j] * d + k2[j] * bf2f(x2v[j]) + z2[j]);
+      o[j] = f2bf(bn_dx(aa[j], d, kk[j], bf2f(xv[j]), zz[j]));
+      o2[j] = f2bf(bn_dx(a2[j], d, k2[j], bf2f(x2v[j]), z2[j]));
     }
     reinterpret_cast<u16x8*>(dx)[v] = o;
     reinterpret_cast<u16x8*>(dx2)[v] = o2;
@@ -807,17 +828,18 @@ static int bn_target_blocks() {
 }
 
 // workspace: part = float[2 * 2048 * C]; stat = float[4 * C] (save_mean, save_invstd, a, b)
+// param_f32 (every training forward): gamma / beta are fp32 (else bf16)
 extern "C" int ct_bn_fwd_train(const void* x, const void* res, const void* gamma, const void* beta,
                                float* run_mean, float* run_var, void* y, float* part, float* stat,
                                int M, int C, float eps, float momentum, int relu, void* mask,
-                               hipStream_t stream) {
+                               int param_f32, hipStream_t stream) {
   if (C % 8 || C / 8 > BN_RT || M <= 0) return -1;
   BnLayout L = bn_layout(M, C, bn_target_blocks());
   const int nblk = bn_nblk(L);
   if (bn_unroll() == 8) bn_stats_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
   else bn_stats_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
   bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)2048 * C, nblk, L,
-                                                           (const bf16_t*)gamma, (const bf16_t*)beta,
+                                                           gamma, beta, param_f32,
                                                            eps, momentum, run_mean, run_var, stat,
                                                            stat + C, stat + 2 * C, stat + 3 * C);
   const long tv = (long)M * (C / 8);
@@ -908,7 +930,7 @@ static int bn_direct_tiles() {
 // merge (when many) + finalize of producer partials into stat = float[4C]
 static void bn_given_finalize(const float* part, int tiles, int rows_per_tile, const void* gamma, const void* beta,
                               float* run_mean, float* run_var, float* stat, int M, int C, float eps, float momentum,
-                              hipStream_t stream) {
+                              int param_f32, hipStream_t stream) {
   if (tiles > std::max(2 * BN_MERGE_GROUP, bn_direct_tiles())) {
     const int groups = ceil_div(tiles, BN_MERGE_GROUP);
     float* om = const_cast<float*>(part) + (size_t)2 * tiles * C;
@@ -920,7 +942,7 @@ static void bn_given_finalize(const float* part, int tiles, int rows_per_tile, c
   }
   BnLayout L{M, C, C / 8, 1, rows_per_tile};
   bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)tiles * C, tiles, L,
-                                                           (const bf16_t*)gamma, (const bf16_t*)beta,
+                                                           gamma, beta, param_f32,
                                                            eps, momentum, run_mean, run_var, stat,
                                                            stat + C, stat + 2 * C, stat + 3 * C);
 }
@@ -931,13 +953,14 @@ extern "C" int ct_bn_fwd_train_given2(const void* x, const void* gamma, const vo
                                       const void* x2, const void* gamma2, const void* beta2, float* run_mean2,
                                       float* run_var2, const float* part2, int tiles2, int rows_per_tile2,
                                       float* stat2, void* y, void* mask, int M, int C, float eps, float momentum,
-                                      hipStream_t stream) {
+                                      int param_f32, hipStream_t stream) {
   if (C % 8 || M <= 0 || tiles <= 0 || tiles2 <= 0 || (long)tiles * rows_per_tile < M ||
       (long)tiles2 * rows_per_tile2 < M || !mask)
     return -1;
-  bn_given_finalize(part, tiles, rows_per_tile, gamma, beta, run_mean, run_var, stat, M, C, eps, momentum, stream);
+  bn_given_finalize(part, tiles, rows_per_tile, gamma, beta, run_mean, run_var, stat, M, C, eps, momentum,
+                    param_f32, stream);
   bn_given_finalize(part2, tiles2, rows_per_tile2, gamma2, beta2, run_mean2, run_var2, stat2, M, C, eps, momentum,
-                    stream);
+                    param_f32, stream);
   const long tv = (long)M * (C / 8);
   bn_apply2_kernel<<<ew_grid(tv, 1), 256, 0, stream>>>((const bf16_t*)x, stat + 2 * C, stat + 3 * C,
                                                        (const bf16_t*)x2, stat2 + 2 * C, stat2 + 3 * C, (bf16_t*)y,
@@ -948,7 +971,7 @@ extern "C" int ct_bn_fwd_train_given2(const void* x, const void* gamma, const vo
 extern "C" int ct_bn_fwd_train_given(const void* x, const void* res, const void* gamma, const void* beta,
                                      float* run_mean, float* run_var, void* y, const float* part, int tiles,
                                      int rows_per_tile, float* stat, int M, int C, float eps, float momentum,
-                                     int relu, void* mask, hipStream_t stream) {
+                                     int relu, void* mask, int param_f32, hipStream_t stream) {
   if (C % 8 || M <= 0 || tiles <= 0 || (long)tiles * rows_per_tile < M) return -1;
   if (tiles > std::max(2 * BN_MERGE_GROUP, bn_direct_tiles())) {
     // merge groups of tiles first, into the tail of the partial buffer (means at
@@ -963,7 +986,7 @@ extern "C" int ct_bn_fwd_train_given(const void* x, const void* res, const void*
   }
   BnLayout L{M, C, C / 8, 1, rows_per_tile};
   bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)tiles * C, tiles, L,
-                                                           (const bf16_t*)gamma, (const bf16_t*)beta,
+                                                           gamma, beta, param_f32,
                                                            eps, momentum, run_mean, run_var, stat,
                                                            stat + C, stat + 2 * C, stat + 3 * C);
   const long tv = (long)M * (C / 8);
@@ -976,7 +999,8 @@ extern "C" int ct_bn_fwd_train_given(const void* x, const void* res, const void*
 // (stat = float[4C] as ct_bn_fwd_train)
 extern "C" int ct_bn_fwd_train_pool(const void* x, const void* gamma, const void* beta, float* run_mean,
                                     float* run_var, void* y, void* arg, float* part, float* stat, int N, int H, int W,
-                                    int C, int OH, int OW, float eps, float momentum, hipStream_t stream) {
+                                    int C, int OH, int OW, float eps, float momentum, int param_f32,
+                                    hipStream_t stream) {
   const int M = N * H * W;
   if (C % 8 || C / 8 > BN_RT || M <= 0 || OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return -1;
   BnLayout L = bn_layout(M, C, bn_target_blocks());
@@ -984,7 +1008,7 @@ extern "C" int ct_bn_fwd_train_pool(const void* x, const void* gamma, const void
   if (bn_unroll() == 8) bn_stats_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
   else bn_stats_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
   bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)2048 * C, nblk, L,
-                                                           (const bf16_t*)gamma, (const bf16_t*)beta,
+                                                           gamma, beta, param_f32,
                                                            eps, momentum, run_mean, run_var, stat,
                                                            stat + C, stat + 2 * C, stat + 3 * C);
   if ((long)N * OH >= (1L << 31)) return -1;
@@ -998,12 +1022,13 @@ extern "C" int ct_bn_fwd_train_pool(const void* x, const void* gamma, const void
 extern "C" int ct_bn_fwd_train_pool_given(const void* x, const void* gamma, const void* beta, float* run_mean,
                                           float* run_var, void* y, void* arg, const float* part, int tiles,
                                           int rows_per_tile, float* stat, int N, int H, int W, int C, int OH, int OW,
-                                          float eps, float momentum, hipStream_t stream) {
+                                          float eps, float momentum, int param_f32, hipStream_t stream) {
   const int M = N * H * W;
   if (C % 8 || M <= 0 || tiles <= 0 || (long)tiles * rows_per_tile < M || OH != (H - 1) / 2 + 1 ||
       OW != (W - 1) / 2 + 1 || (long)N * OH >= (1L << 31))
     return -1;
-  bn_given_finalize(part, tiles, rows_per_tile, gamma, beta, run_mean, run_var, stat, M, C, eps, momentum, stream);
+  bn_given_finalize(part, tiles, rows_per_tile, gamma, beta, run_mean, run_var, stat, M, C, eps, momentum, param_f32,
+                    stream);
   bn_apply_pool_kernel<<<N * OH, 256, 0, stream>>>((const bf16_t*)x, stat + 2 * C, stat + 3 * C, (bf16_t*)y,
                                                    (uint8_t*)arg, N, H, W, C / 8, OH, OW);
   return hipGetLastError() == hipSuccess ? 0 : 7;
@@ -1073,7 +1098,7 @@ extern "C" int ct_bn_bwd(const void* dy, const void* y, const void* x, const voi
   const int acc = (param_flags >> 1) & 1;   // bit 1: accumulate into dgamma / dbeta
   if (param_flags & 1)
     bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        part, part + (size_t)2048 * C, nblk, M, C, (const bf16_t*)gamma, stat, stat + C,
+        part, part + (size_t)2048 * C, nblk, M, C, (const float*)gamma, stat, stat + C,
         (float*)dgamma, (float*)dbeta, coef, coef + C, coef + 2 * C, acc);
   else
     bn_bwd_finalize_kernel<bf16_t><<<ceil_div(C, 64), 1024, 0, stream>>>(
@@ -1163,10 +1188,10 @@ extern "C" int ct_bn_bwd_given_pair(const void* dym, const void* x, const void* 
   const int acc = (param_flags >> 1) & 1;
   if (param_flags & 1) {
     bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        q1, q2, nq, M, C, (const bf16_t*)gamma, stat, stat + C, (float*)dgamma, (float*)dbeta, coef, coef + C,
+        q1, q2, nq, M, C, (const float*)gamma, stat, stat + C, (float*)dgamma, (float*)dbeta, coef, coef + C,
         coef + 2 * C, acc);
     bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        part2, part2 + (size_t)2048 * C, nblk, M, C, (const bf16_t*)gamma2, stat2, stat2 + C, (float*)dgamma2,
+        part2, part2 + (size_t)2048 * C, nblk, M, C, (const float*)gamma2, stat2, stat2 + C, (float*)dgamma2,
         (float*)dbeta2, coef2, coef2 + C, coef2 + 2 * C, acc);
   } else {
     bn_bwd_finalize_kernel<bf16_t><<<ceil_div(C, 64), 1024, 0, stream>>>(
@@ -1202,7 +1227,7 @@ extern "C" int ct_bn_bwd_given(const void* dym, const void* x, const void* gamma
   const int acc = (param_flags >> 1) & 1;
   if (param_flags & 1)
     bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        q1, q2, nq, M, C, (const bf16_t*)gamma, stat, stat + C, (float*)dgamma, (float*)dbeta, coef, coef + C,
+        q1, q2, nq, M, C, (const float*)gamma, stat, stat + C, (float*)dgamma, (float*)dbeta, coef, coef + C,
         coef + 2 * C, acc);
   else
     bn_bwd_finalize_kernel<bf16_t><<<ceil_div(C, 64), 1024, 0, stream>>>(

@@ -44,18 +44,18 @@ int ct_clip_coef(const float*, float*, float, float, hipStream_t);
 int ct_xent_fwd(const void*, void*, int, int, const int64_t*, float*, float*, const float*, int, int,
                 float, hipStream_t);
 int ct_bn_fwd_train(const void*, const void*, const void*, const void*, float*, float*, void*, float*,
-                    float*, int, int, float, float, int, void*, hipStream_t);
+                    float*, int, int, float, float, int, void*, int, hipStream_t);
 int ct_bn_apply(const void*, const void*, const float*, const float*, void*, int, int, int, hipStream_t);
 int ct_bn_fwd_train_given(const void*, const void*, const void*, const void*, float*, float*, void*, const float*, int,
-                          int, float*, int, int, float, float, int, void*, hipStream_t);
+                          int, float*, int, int, float, float, int, void*, int, hipStream_t);
 int ct_bn_fwd_train_pool_given(const void*, const void*, const void*, float*, float*, void*, void*, const float*, int, int,
-                               float*, int, int, int, int, int, int, float, float, hipStream_t);
+                               float*, int, int, int, int, int, int, float, float, int, hipStream_t);
 int ct_bn_fwd_train_pool(const void*, const void*, const void*, float*, float*, void*, void*, float*, float*, int, int,
-                         int, int, int, int, float, float, hipStream_t);
+                         int, int, int, int, float, float, int, hipStream_t);
 int ct_maxpool3s2_bwd(const void*, const void*, void*, int, int, int, int, int, int, hipStream_t);
 int ct_bn_fwd_train_given2(const void*, const void*, const void*, float*, float*, const float*, int, int, float*,
                            const void*, const void*, const void*, float*, float*, const float*, int, int, float*,
-                           void*, void*, int, int, float, float, hipStream_t);
+                           void*, void*, int, int, float, float, int, hipStream_t);
 int ct_maxpool3s2_bwd_bn(const void*, const void*, const void*, const float*, void*, float*, int, int, int, int, int,
                          int, hipStream_t);
 long ct_maxpool3s2_bwd_bn_rows(int, int);
@@ -511,6 +511,18 @@ static void* mask_ptr(const c10::optional<at::Tensor>& mask, const at::Tensor& x
   return mask->data_ptr();
 }
 
+// gamma / beta (and the gamma of a backward) arrive in bf16 or in fp32 -- BatchNorm parameters kept
+// in fp32 beside bf16 activations -- and the kernels read them in that dtype: 1 when fp32
+static int bn_param_f32(const at::Tensor& gamma, const char* name) {
+  TORCH_CHECK(gamma.is_cuda() && (gamma.scalar_type() == at::kBFloat16 || gamma.scalar_type() == at::kFloat), name,
+              ": BatchNorm parameters must be bf16 or fp32 CUDA tensors");
+  return gamma.scalar_type() == at::kFloat ? 1 : 0;
+}
+static int bn_param_f32(const at::Tensor& gamma, const at::Tensor& beta, const char* name) {
+  TORCH_CHECK(beta.is_cuda() && beta.scalar_type() == gamma.scalar_type(), name, ": gamma and beta must share a dtype");
+  return bn_param_f32(gamma, name);
+}
+
 // returns (y, stat) with stat = float[4C]: save_mean, save_invstd, a, b (y = x * a + b ...);
 // mask_out (optional, uint8 [numel / 8]) receives the ReLU bitmask (bit j of byte v: y > 0)
 std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor gamma,
@@ -524,13 +536,14 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res
   if (res.has_value() && res->defined()) { check_nhwc(*res, "residual"); TORCH_CHECK(res->sizes() == x.sizes()); }
   TORCH_CHECK(gamma.numel() == C && beta.numel() == C && run_mean.numel() == C && run_var.numel() == C);
   CHECK_F32(run_mean); CHECK_F32(run_var);
+  const int pf32 = bn_param_f32(gamma, beta, "bn_fwd_train");
   auto y = at::empty_like(x);
   auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
   auto part = at::empty({2 * 2048 * (long)C}, x.options().dtype(at::kFloat));
   int rc = ct_bn_fwd_train(x.data_ptr(), optr(res), gamma.data_ptr(), beta.data_ptr(),
                            run_mean.data_ptr<float>(), run_var.data_ptr<float>(), y.data_ptr(),
                            part.data_ptr<float>(), stat.data_ptr<float>(), (int)M, C, (float)eps,
-                           (float)momentum, relu ? 1 : 0, mask_ptr(mask_out, x), cur_stream());
+                           (float)momentum, relu ? 1 : 0, mask_ptr(mask_out, x), pf32, cur_stream());
   TORCH_CHECK(rc == 0, "bn_fwd_train: unsupported C=", C);
   return {y, stat};
 }
@@ -551,13 +564,14 @@ std::vector<at::Tensor> bn_fwd_train_given(at::Tensor x, c10::optional<at::Tenso
   // the tail holds the first-level merge (ct_bn_fwd_train_given) when there are many tiles
   TORCH_CHECK(part.numel() >= 2 * (tiles + (tiles > 128 ? (tiles + 63) / 64 : 0)) * C,
               "bn_fwd_train_given: part buffer");
+  const int pf32 = bn_param_f32(gamma, beta, "bn_fwd_train_given");
   auto y = at::empty_like(x);
   auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
   int rc = ct_bn_fwd_train_given(x.data_ptr(), optr(res), gamma.data_ptr(), beta.data_ptr(),
                                  run_mean.data_ptr<float>(), run_var.data_ptr<float>(), y.data_ptr(),
                                  part.data_ptr<float>(), (int)tiles, (int)rows_per_tile, stat.data_ptr<float>(),
                                  (int)M, C, (float)eps, (float)momentum, relu ? 1 : 0, mask_ptr(mask_out, x),
-                                 cur_stream());
+                                 pf32, cur_stream());
   TORCH_CHECK(rc == 0, "bn_fwd_train_given: unsupported C=", C);
   return {y, stat};
 }
@@ -582,6 +596,8 @@ std::vector<at::Tensor> bn_fwd_train_given2(at::Tensor x, at::Tensor gamma, at::
   TORCH_CHECK(part.numel() >= 2 * (tiles + (tiles > 128 ? (tiles + 63) / 64 : 0)) * C &&
               part2.numel() >= 2 * (tiles2 + (tiles2 > 128 ? (tiles2 + 63) / 64 : 0)) * C,
               "bn_fwd_train_given2: part buffers");
+  const int pf32 = bn_param_f32(gamma, beta, "bn_fwd_train_given2");
+  TORCH_CHECK(bn_param_f32(gamma2, beta2, "bn_fwd_train_given2") == pf32, "bn_fwd_train_given2: parameter dtypes");
   auto y = at::empty_like(x);
   auto mask = at::empty({x.numel() / 8}, x.options().dtype(at::kByte));
   auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
@@ -591,7 +607,7 @@ std::vector<at::Tensor> bn_fwd_train_given2(at::Tensor x, at::Tensor gamma, at::
                                   stat.data_ptr<float>(), x2.data_ptr(), gamma2.data_ptr(), beta2.data_ptr(),
                                   run_mean2.data_ptr<float>(), run_var2.data_ptr<float>(), part2.data_ptr<float>(),
                                   (int)tiles2, (int)rows_per_tile2, stat2.data_ptr<float>(), y.data_ptr(),
-                                  mask.data_ptr(), (int)M, C, (float)eps, (float)momentum, cur_stream());
+                                  mask.data_ptr(), (int)M, C, (float)eps, (float)momentum, pf32, cur_stream());
   TORCH_CHECK(rc == 0, "bn_fwd_train_given2: unsupported C=", C);
   return {y, mask, stat, stat2};
 }
@@ -615,7 +631,9 @@ std::vector<at::Tensor> bn_bwd_given_pair(at::Tensor dym, at::Tensor x, at::Tens
   TORCH_CHECK(C <= 2048 && stat.numel() == 4 * (long)C && stat2.numel() == 4 * (long)C, "bn_bwd_given_pair: stat");
   CHECK_F32(stat); CHECK_F32(stat2); CHECK_F32(part);
   TORCH_CHECK(tiles > 0 && tiles <= rows && part.numel() >= 2 * rows * C, "bn_bwd_given_pair: part buffer");
-  TORCH_CHECK(gamma2.scalar_type() == gamma.scalar_type(), "bn_bwd_given_pair: parameter dtypes");
+  TORCH_CHECK(gamma2.scalar_type() == gamma.scalar_type() && gamma.numel() == C && gamma2.numel() == C,
+              "bn_bwd_given_pair: parameter dtypes");
+  const int pf32 = bn_param_f32(gamma, "bn_bwd_given_pair");
   const bool acc = dgamma_acc.has_value() && dgamma_acc->defined();
   for (const auto* t : {&dbeta_acc, &dgamma2_acc, &dbeta2_acc})
     TORCH_CHECK((t->has_value() && (*t)->defined()) == acc, "bn_bwd_given_pair: accumulate targets: all or none");
@@ -635,7 +653,7 @@ std::vector<at::Tensor> bn_bwd_given_pair(at::Tensor dym, at::Tensor x, at::Tens
                                 part.data_ptr<float>(), rows * C, (int)tiles, x2.data_ptr(), gamma2.data_ptr(),
                                 stat2.data_ptr<float>(), dx.data_ptr(), dx2.data_ptr(), dg.data_ptr(), db.data_ptr(),
                                 dg2.data_ptr(), db2.data_ptr(),
-                                (gamma.scalar_type() == at::kFloat ? 1 : 0) | (acc ? 2 : 0), work.data_ptr<float>(),
+                                pf32 | (acc ? 2 : 0), work.data_ptr<float>(),
                                 part2.data_ptr<float>(), coef2.data_ptr<float>(), (int)M, C, cur_stream());
   TORCH_CHECK(rc == 0, "bn_bwd_given_pair: unsupported C=", C);
   return {dx, dx2, dg, db, dg2, db2};
@@ -657,7 +675,8 @@ std::vector<at::Tensor> bn_fwd_train_pool(at::Tensor x, at::Tensor gamma, at::Te
   auto part = at::empty({2 * 2048 * (long)C}, x.options().dtype(at::kFloat));
   int rc = ct_bn_fwd_train_pool(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), run_mean.data_ptr<float>(),
                                 run_var.data_ptr<float>(), y.data_ptr(), arg.data_ptr(), part.data_ptr<float>(),
-                                stat.data_ptr<float>(), N, H, W, C, OH, OW, (float)eps, (float)momentum, cur_stream());
+                                stat.data_ptr<float>(), N, H, W, C, OH, OW, (float)eps, (float)momentum,
+                                bn_param_f32(gamma, beta, "bn_fwd_train_pool"), cur_stream());
   TORCH_CHECK(rc == 0, "bn_fwd_train_pool: unsupported shape");
   return {y, arg, stat};
 }
@@ -685,7 +704,8 @@ std::vector<at::Tensor> bn_fwd_train_pool_given(at::Tensor x, at::Tensor gamma, 
   int rc = ct_bn_fwd_train_pool_given(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), run_mean.data_ptr<float>(),
                                       run_var.data_ptr<float>(), y.data_ptr(), arg.data_ptr(), part.data_ptr<float>(),
                                       (int)tiles, (int)rows_per_tile, stat.data_ptr<float>(), N, H, W, C, OH, OW,
-                                      (float)eps, (float)momentum, cur_stream());
+                                      (float)eps, (float)momentum, bn_param_f32(gamma, beta, "bn_fwd_train_pool_given"),
+                                      cur_stream());
   TORCH_CHECK(rc == 0, "bn_fwd_train_pool_given: unsupported shape");
   return {y, arg, stat};
 }
@@ -753,6 +773,8 @@ std::vector<at::Tensor> bn_bwd(at::Tensor dy, c10::optional<at::Tensor> y, at::T
   TORCH_CHECK(C <= 2048 && stat.numel() == 4 * (long)C, "bn_bwd: stat must be float[4C], C <= 2048");
   CHECK_F32(stat);
   TORCH_CHECK(relu_mode >= 0 && relu_mode <= 3, "bn_bwd: relu_mode 0/1/2/3");
+  TORCH_CHECK(gamma.numel() == C, "bn_bwd: gamma must have C elements");
+  const int pf32 = bn_param_f32(gamma, "bn_bwd");
   if (relu_mode == 1) {
     TORCH_CHECK(y.has_value() && y->defined(), "bn_bwd: relu_mode 1 needs y");
     check_nhwc(*y, "y");
@@ -780,7 +802,7 @@ std::vector<at::Tensor> bn_bwd(at::Tensor dy, c10::optional<at::Tensor> y, at::T
                      gamma.data_ptr(),
                      stat.data_ptr<float>(), dx.data_ptr(), need_dres ? dres.data_ptr() : nullptr,
                      dgamma.data_ptr(), dbeta.data_ptr(),
-                     (gamma.scalar_type() == at::kFloat ? 1 : 0) | (acc ? 2 : 0), part.data_ptr<float>(),
+                     pf32 | (acc ? 2 : 0), part.data_ptr<float>(),
                      coef.data_ptr<float>(), (int)M, C, (int)relu_mode, cur_stream());
   TORCH_CHECK(rc == 0, "bn_bwd: unsupported C=", C);
   return {dx, dres, dgamma, dbeta};
@@ -801,6 +823,8 @@ std::vector<at::Tensor> bn_bwd_given(at::Tensor dym, at::Tensor x, at::Tensor ga
   CHECK_F32(stat);
   CHECK_F32(part);
   TORCH_CHECK(tiles > 0 && tiles <= rows && part.numel() >= 2 * rows * C, "bn_bwd_given: part buffer");
+  TORCH_CHECK(gamma.numel() == C, "bn_bwd_given: gamma must have C elements");
+  const int pf32 = bn_param_f32(gamma, "bn_bwd_given");
   const bool acc = dgamma_acc.has_value() && dgamma_acc->defined();
   if (acc) {
     TORCH_CHECK(dbeta_acc.has_value() && dbeta_acc->defined(), "bn_bwd_given: dgamma_acc needs dbeta_acc");
@@ -814,7 +838,7 @@ std::vector<at::Tensor> bn_bwd_given(at::Tensor dym, at::Tensor x, at::Tensor ga
   auto work = at::empty({2 * G * C + 3 * (long)C}, x.options().dtype(at::kFloat));
   int rc = ct_bn_bwd_given(dym.data_ptr(), x.data_ptr(), gamma.data_ptr(), stat.data_ptr<float>(), dx.data_ptr(),
                            dgamma.data_ptr(), dbeta.data_ptr(),
-                           (gamma.scalar_type() == at::kFloat ? 1 : 0) | (acc ? 2 : 0), part.data_ptr<float>(),
+                           pf32 | (acc ? 2 : 0), part.data_ptr<float>(),
                            rows * C, (int)tiles, work.data_ptr<float>(), (int)M, C, cur_stream());
   TORCH_CHECK(rc == 0, "bn_bwd_given: unsupported C=", C);
   return {dx, dgamma, dbeta};
@@ -832,6 +856,7 @@ std::vector<at::Tensor> bn_bwd_coefs_given(int64_t M, at::Tensor gamma, at::Tens
   CHECK_F32(stat);
   CHECK_F32(part);
   TORCH_CHECK(M > 0 && tiles > 0 && tiles <= rows && part.numel() >= 2 * rows * C, "bn_bwd_coefs_given: part buffer");
+  const int pf32 = bn_param_f32(gamma, "bn_bwd_coefs_given");
   const bool acc = dgamma_acc.has_value() && dgamma_acc->defined();
   if (acc) {
     TORCH_CHECK(dbeta_acc.has_value() && dbeta_acc->defined() && dgamma_acc->is_contiguous() &&
@@ -843,7 +868,7 @@ std::vector<at::Tensor> bn_bwd_coefs_given(int64_t M, at::Tensor gamma, at::Tens
   const long G = (tiles + 63) / 64;
   auto work = at::empty({2 * G * C + 3 * (long)C}, gamma.options().dtype(at::kFloat));
   int rc = ct_bn_bwd_given(nullptr, nullptr, gamma.data_ptr(), stat.data_ptr<float>(), nullptr, dgamma.data_ptr(),
-                           dbeta.data_ptr(), (gamma.scalar_type() == at::kFloat ? 1 : 0) | (acc ? 2 : 0),
+                           dbeta.data_ptr(), pf32 | (acc ? 2 : 0),
                            part.data_ptr<float>(), rows * C, (int)tiles, work.data_ptr<float>(), (int)M, C, cur_stream());
   TORCH_CHECK(rc == 0, "bn_bwd_coefs_given: unsupported C=", C);
   return {dgamma, dbeta, work.narrow(0, 2 * G * C, 3 * (long)C)};

@@ -364,7 +364,8 @@ def batch_norm_add_bn_act(x, weight, bias, running_mean, running_var, x2, weight
     epilogue statistics (``_ct_bn_part``), else the two-step form."""
     if (_BN_ADD_BN_FUSE and _native(x) and x.dim() == 4 and x2.shape == x.shape
             and getattr(x, "_ct_bn_part", None) is not None and getattr(x2, "_ct_bn_part", None) is not None
-            and x.stride() == x2.stride() and x.numel() % 8 == 0):
+            and x.stride() == x2.stride() and x.numel() % 8 == 0
+            and _bn_params_ok(weight, bias, weight2, bias2)):
         return _BNAddBNActFn.apply(x, weight, bias, running_mean, running_var, x2, weight2, bias2, running_mean2,
                                    running_var2, float(momentum), float(eps))
     idt = batch_norm_act(x2, weight2, bias2, running_mean2, running_var2, relu=False, training=True,
@@ -557,7 +558,7 @@ def stem_block(x, conv, bn):
 
 def batch_norm_relu_maxpool(x, weight, bias, running_mean, running_var, training=True, momentum=0.1, eps=1e-5):
     """``max_pool2d(relu(BatchNorm(x)), 3, 2, 1)`` -- fused on GPU in training (NHWC bf16)."""
-    if _native(x) and _bn_native_ok(x) and x.dim() == 4 and training:
+    if _native(x) and _bn_native_ok(x, weight, bias) and x.dim() == 4 and training:
         return _BNReLUPoolFn.apply(x, weight, bias, running_mean, running_var, float(momentum), float(eps))
     y = batch_norm_act(x, weight, bias, running_mean, running_var, relu=True, training=training,
                        momentum=momentum, eps=eps)
@@ -588,8 +589,16 @@ class _BNAffineFn(torch.autograd.Function):
         return dx, None, None, (g if has_res else None), None
 
 
-def _bn_native_ok(x):
+def _bn_params_ok(*params):
+    """gamma / beta as the kernels read them: all bf16 or all fp32, on the GPU."""
+    dt = params[0].dtype
+    return dt in (torch.bfloat16, torch.float32) and all(p.dtype == dt and p.is_cuda for p in params)
+
+
+def _bn_native_ok(x, *params):
     if x.dtype != torch.bfloat16 or x.dim() not in (2, 4):
+        return False
+    if params and not _bn_params_ok(*params):
         return False
     C = x.shape[1]
     if C % 8 or C > 2048:
@@ -600,7 +609,7 @@ def _bn_native_ok(x):
 def batch_norm_act(x, weight, bias, running_mean, running_var, residual=None, relu=True,
                    training=True, momentum=0.1, eps=1e-5):
     """relu(BatchNorm(x) + residual) over NHWC/channels_last bf16 (training: batch stats)."""
-    if _native(x) and _bn_native_ok(x) and training and (
+    if _native(x) and _bn_native_ok(x, weight, bias) and training and (
             residual is None or residual.is_contiguous(memory_format=torch.channels_last)
             or (x.dim() == 2 and residual.is_contiguous())):
         return _BNActFn.apply(x, weight, bias, residual, running_mean, running_var, bool(relu),
