@@ -1,4 +1,4 @@
-"""T5 encoder-decoder (t5-small / base / large topologies).
+"""T5 encoder-decoder (t5-small / base / large / 3b / 11b topologies; 3b and 11b have d_kv = 128).
 
 Reference workload: the quickstart T5 inference (applications/ai/quickstart, HF
 ``T5ForConditionalGeneration``).  Random-init weights or a local HF
@@ -12,7 +12,8 @@ position bias is carried as one [H, Sq + Sk - 1] vector per stack (bias depends 
 key - query) and added inside the MFMA flash-attention kernel (``ops.attention_relbias``),
 so inference never materialises an [H, Sq, Sk] bias; cross-attention uses the MFMA kernel
 with the per-key padding mask; training self-attention (which needs the bias gradient) uses
-SDPA with the gathered bias; the training loss is the fused linear + cross-entropy HIP
+SDPA with the gathered bias, as does every attention that needs a gradient at d_kv = 128 (the
+head-dim-128 kernel is forward only); the training loss is the fused linear + cross-entropy HIP
 kernel over the 32128-token vocabulary; generation keeps a per-layer KV cache and replays
 the decode step as a HIP graph, greedy, with beam search (``ops/beam.py``, ``csrc/beam.hip``) or
 sampling (``ops/sampling.py``, ``csrc/sampling.hip``), each with the history-dependent token bans of
@@ -67,6 +68,16 @@ class T5Config:
     @classmethod
     def large(cls, **kw):
         return cls(d_model=1024, d_ff=4096, num_layers=24, num_decoder_layers=24, num_heads=16, **kw)
+
+    @classmethod
+    def xl(cls, **kw):
+        """t5-3b."""
+        return cls(d_model=1024, d_kv=128, d_ff=16384, num_layers=24, num_decoder_layers=24, num_heads=32, **kw)
+
+    @classmethod
+    def xxl(cls, **kw):
+        """t5-11b."""
+        return cls(d_model=1024, d_kv=128, d_ff=65536, num_layers=24, num_decoder_layers=24, num_heads=128, **kw)
 
     @classmethod
     def tiny(cls, **kw):
@@ -193,7 +204,9 @@ class T5Attention(nn.Module):
                 k, v = torch.cat([cache[0], k], 1), torch.cat([cache[1], v], 1)
         Sk = k.shape[1]
         grad = torch.is_grad_enabled() and self.training
-        kernel_ok = q.is_cuda and q.dtype == torch.bfloat16 and self.dk == 64
+        kernel_ok = q.is_cuda and q.dtype == torch.bfloat16 and self.dk in (64, 128)
+        if self.dk == 128 and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+            kernel_ok = False                     # the head-dim-128 kernel is forward only: SDPA below
         # causal masking in the kernel is top-left aligned: exact for prefill (offset 0) and for
         # single-token decode steps (every cached key is visible)
         causal = self.causal and S > 1

@@ -7,7 +7,8 @@ Two entry points:
   strides), returns ``[B, S, H*64]`` ready for the output projection, and its backward
   writes dQ, dK, dV into ONE packed ``[B, S, 3*H*64]`` gradient so the QKV projection's
   backward is a single GEMM.
-* :func:`attention` -- generic ``[B, H, S, D]`` tensors (torch SDPA layout).
+* :func:`attention` -- generic ``[B, H, S, D]`` tensors (torch SDPA layout).  D = 64 trains;
+  D = 128 takes the forward-only kernel when the call needs neither a gradient nor dropout.
 
 ``key_bias`` is an additive fp32 ``[B, Sk]`` per-key bias (HF BERT: ``(1 - mask) * -10000``).
 """
@@ -81,6 +82,13 @@ def _native_ok(t, D):
     return t.is_cuda and t.dtype == torch.bfloat16 and D == 64
 
 
+def _fwd_only_d128(q, k, v, p):
+    """A D = 128 call the forward-only kernel may take: bf16 on the GPU, no dropout, and
+    nothing autograd would record."""
+    return (q.is_cuda and q.dtype == torch.bfloat16 and p == 0
+            and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)))
+
+
 def attention_packed(qkv, num_heads, key_bias=None, p=0.0, training=True, scale=None,
                      causal=False):
     """qkv: [B, S, 3*H*D] -> [B, S, H*D]."""
@@ -108,6 +116,13 @@ def attention(q, k, v, key_bias=None, p=0.0, scale=None, causal=False):
     seed, offset = ops._rng.next(B * H * Sq * Sk) if p > 0 else (0, 0)
     if key_bias is not None:
         key_bias = key_bias.float().contiguous()
+    if D == 128 and _fwd_only_d128(q, k, v, p) and ops._use_native(q):
+        # head dim 128: inference kernel only (no backward, no dropout), so not through _AttnFn
+        qt = q.transpose(1, 2)
+        o = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+        ops.require_native().attn_fwd(qt, k.transpose(1, 2), v.transpose(1, 2), o, key_bias, scale, 0.0, 0, 0,
+                                      bool(causal))
+        return o.transpose(1, 2)
     if ops._use_native(q) and _native_ok(q, D) and (p == 0 or Sk % 2 == 0):
         o = _AttnFn.apply(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), key_bias, scale,
                           float(p), seed, offset, bool(causal))
@@ -118,11 +133,11 @@ def attention(q, k, v, key_bias=None, p=0.0, scale=None, causal=False):
 def attention_relbias(q, k, v, rel_bias, rel_base: int, key_bias=None, scale: float = 1.0, causal: bool = False):
     """Inference attention with a relative-position bias (T5): q/k/v ``[B, S, H, D]``,
     ``rel_bias [H, L]`` adds ``rel_bias[h, k - q + rel_base]`` to every score (natural-log
-    units), ``key_bias [B, Sk]`` masks keys.  HIP MFMA kernel on the GPU (bf16, D = 64);
+    units), ``key_bias [B, Sk]`` masks keys.  HIP MFMA kernel on the GPU (bf16, D = 64 or 128);
     fp32 PyTorch reference elsewhere.  Forward only."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
-    if (q.is_cuda and q.dtype == torch.bfloat16 and D == 64 and rel_bias.shape[1] <= 4096
+    if (q.is_cuda and q.dtype == torch.bfloat16 and D in (64, 128) and rel_bias.shape[1] <= 4096
             and _ops().native_available()):
         o = torch.empty_like(q)
         kb = key_bias.float().contiguous() if key_bias is not None else None

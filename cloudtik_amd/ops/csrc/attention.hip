@@ -1,4 +1,6 @@
-// Fused multi-head attention (forward + backward) on CDNA4 MFMA, head_dim 64, bf16 I/O.
+// Fused multi-head attention on CDNA4 MFMA, bf16 I/O: forward + backward at head_dim 64, and an
+// inference forward at head_dim 128 (attn_fwd_d128_kernel: T5-3B / T5-11B, d_kv = 128; forward
+// only, no dropout; its header comment states its LDS plan).
 //
 // Hot op of the reference's BERT-large pretraining: HF BertSelfAttention, 16 heads x 64,
 // S = 128 (phase-1 shards) / 512, padding mask + attention-prob dropout 0.1
@@ -32,6 +34,10 @@
 //     keys (S <= 128, the BERT phase-1 case), otherwise accumulated with fp32 atomics and
 //     converted by a tiny kernel.
 //   * attention-prob dropout regenerated from a counter hash (nothing stored).
+// Head dim 128 (attn_fwd_d128_kernel<CAUSAL, REL>): the forward above with 8 k-steps for S^T and
+// four O^T blocks; a K/V tile is two 64-column halves in the d64 LDS image; K/V by
+// global_load_lds into a two-deep ring; the relative-bias stage is dynamic LDS sized to the
+// vector, so two workgroups share a CU.
 #include "common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -585,6 +591,217 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnFwdArgs a) {
   }
 }
 
+// at_glds16s for the d128 kernel.  Its REL instantiations keep the K/V base pointers in VGPRs, so
+// the readfirstlanes below are real VALU writes of the SGPR pair the load reads as its scalar
+// base, and the compiler does not pad that hazard around inline asm (5 wait states; what
+// scripts/isa_audit.py checks): s_mov + s_nop 3 are the 5.
+__device__ __forceinline__ void at_glds16s_pad(const void* sbase, unsigned voff, const char* lds_wave_base) {
+  const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(at_lds_void*)lds_wave_base);
+  const uint64_t sb = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)sbase) |
+                      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)sbase >> 32)) << 32);
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sb), "s"(la)
+               : "memory", "m0");
+}
+
+// Head-dim-128 inference forward (T5-3B / T5-11B: d_kv = 128): forward only, no dropout.
+// Semantics of attn_fwd_d64_kernel<false, CAUSAL, REL>: fp32 key bias, optional relative-bias
+// vector, top-left causal mask, exp2-domain online softmax, o bf16 + lse fp32 (log2 domain),
+// a fully masked row gives o = 0 and lse = +inf.  Same query-on-the-lane structure:
+// 4 waves x 32 queries, S^T = K . Q^T in 8 k-steps (qf[8]), the P^T accumulators feed
+// O^T += V^T . P^T, O^T is four f32x16 blocks (d 0..31, 32..63, 64..95, 96..127).
+//
+// LDS image: a 64-key x 128-d tile is two 64-column halves, each the d64 kernel's
+// [64 rows][128 B] image under the same swz(): k-steps 0..3 / O blocks 0, 1 read half 0,
+// k-steps 4..7 / O blocks 2, 3 read half 1, so the ds_read_b128 row reads and the
+// ds_read_tr16_b64 column reads keep the d64 kernel's conflict-free pattern.
+//
+// LDS plan: 64-key tiles, K and V both double-buffered (2 x (16 KB + 16 KB) = 64 KB) plus
+// 512 B of key bias, and the relative-bias stage sized to relb_len at launch (dynamic LDS,
+// 4 relb_len bytes) instead of a fixed kRelBiasMax x 4 = 16 KB.  Why: with the fixed stage a
+// workgroup takes 80.5 KB and ONE fits in a CU's 160 KB, so its tile loads overlap nobody's
+// MFMAs; T5's vectors are Sq + Sk - 1 floats (a few hundred to ~1 K), and at
+// relb_len <= 3968 a workgroup stays under 80 KB and TWO fit, which is also all the
+// 2-waves-per-SIMD register budget allows.  The ring keeps the d64 kernel's one barrier per
+// tile (a single-buffered V needs a second one) and its 64-key softmax step (32-key tiles
+// double the number of rescales and barriers).  Cost: one workgroup per CU for the non-T5
+// case 3968 < relb_len <= 4096, and never the three per CU the d64 kernel reaches.
+//
+// K/V tiles go global -> LDS by global_load_lds (at_glds16s_pad), wave w rows 16 w .. 16 w + 15
+// of both halves of K and V (eight 1 KB wave instructions a tile), no staging registers.
+// Keys past Sk re-read key Sk - 1 and are killed by their -inf key bias: no load is out of
+// bounds.  Both tiles of an Sk <= 128 call are loaded up front (no barrier in the loop).
+// A wave none of whose 32 queries exists (the decode shape: Sq = 1) still loads its share of
+// every tile and meets every barrier, but skips the MFMAs and the softmax.
+template <bool CAUSAL, bool REL>
+__global__ __launch_bounds__(256, 2) void attn_fwd_d128_kernel(AttnFwdArgs a) {
+  // [buf][K half 0, K half 1, V half 0, V half 1][64 rows][128 B], then [buf][64] fp32
+  // log2-domain key bias (-inf past Sk)
+  __shared__ __attribute__((aligned(16))) char smem[2 * 4 * 64 * 128 + 2 * 64 * 4];
+  float* kbias_lds = reinterpret_cast<float*>(smem + 65536);
+  // one head's relative-position bias vector, log2-scaled: relb_len floats of dynamic LDS
+  // (REL only; the first K/V tile's barrier below publishes it)
+  extern __shared__ float relb_dyn[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hh = lane >> 5;
+  const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
+  const int qi = blockIdx.x * 128 + w * 32 + r;
+  const bool qvalid = qi < a.Sq;
+  const bool wactive = (int)blockIdx.x * 128 + w * 32 < a.Sq;   // wave-uniform
+  const float LOG2E = 1.4426950408889634f;
+  if (REL)
+    for (int i = tid; i < a.relb_len; i += 256) relb_dyn[i] = a.relb[h * a.relb_sh + i] * LOG2E;
+
+  const bf16_t* qp = a.q + b * a.q_sb + h * a.q_sh + (long)qi * a.q_ss;
+  bf16x8_t qf[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) qf[s] = gload_frag(qp + 16 * s + 8 * hh, qvalid);
+
+  const bf16_t* kp = a.k + b * a.k_sb + h * a.k_sh;
+  const bf16_t* vp = a.v + b * a.v_sb + h * a.v_sh;
+  const float* kbp = a.kbias ? a.kbias + b * a.kb_sb : nullptr;
+  float stB = 0.f;
+
+  f32x16 O[4];
+#pragma unroll
+  for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) O[ob][i] = 0.f;
+  float m = -INFINITY, l = 0.f;
+  const int nt = (a.Sk + 63) / 64;
+  const bool resident = nt == 2;
+
+  // lane l lands at physical chunk l & 7 of row 16 w + 8 i + (l >> 3) of the half, so it
+  // fetches logical chunk (l & 7) ^ rev3((4 i + (l >> 4)) & 7): the swz() image
+#define FWD128_GLDS(kt_, buf_)                                                                 \
+  _Pragma("unroll") for (int hf_ = 0; hf_ < 2; ++hf_)                                          \
+  _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                           \
+    const int row_ = 16 * w + 8 * i_ + (lane >> 3);                                            \
+    const unsigned key_ = (unsigned)min((kt_) * 64 + row_, a.Sk - 1);                          \
+    const unsigned c_ = (unsigned)((lane & 7) ^ rev3((4 * i_ + (lane >> 4)) & 7));             \
+    char* dst_ = smem + (buf_) * 32768 + hf_ * 8192 + (16 * w + 8 * i_) * 128;                 \
+    at_glds16s_pad(kp, (key_ * (unsigned)a.k_ss + 64u * hf_ + c_ * 8u) * 2u, dst_);                \
+    at_glds16s_pad(vp, (key_ * (unsigned)a.v_ss + 64u * hf_ + c_ * 8u) * 2u, dst_ + 16384);        \
+  }
+  FWD128_GLDS(0, 0);
+  if (resident) {
+    FWD128_GLDS(1, 1);
+    if (tid < 128) stB = tid < a.Sk ? (kbp ? kbp[tid] * LOG2E : 0.f) : -INFINITY;
+  } else if (tid < 64) {
+    stB = tid < a.Sk ? (kbp ? kbp[tid] * LOG2E : 0.f) : -INFINITY;
+  }
+  if (tid < (resident ? 128 : 64)) kbias_lds[tid] = stB;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  const int trow = (lane >> 2) & 3;
+  const int tcol = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
+
+  for (int kt = 0; kt < nt; ++kt) {
+    const int buf = kt & 1;
+    if (!resident && kt + 1 < nt) {
+      // buf ^ 1 was last read in tile kt - 1, which ended with a barrier
+      FWD128_GLDS(kt + 1, buf ^ 1);
+      if (tid < 64) {
+        const int kk = (kt + 1) * 64 + tid;
+        stB = kk < a.Sk ? (kbp ? kbp[kk] * LOG2E : 0.f) : -INFINITY;
+      }
+    }
+    if (wactive) {
+      const char* Kb = smem + buf * 32768;
+      const char* Vb = Kb + 16384;
+      f32x16 S0, S1;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { S0[i] = 0.f; S1[i] = 0.f; }
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const char* Kh = Kb + (s >> 2) * 8192;
+        S0 = mfma32(lds_b128(Kh + swz(r, 2 * (s & 3) + hh)), qf[s], S0);
+        S1 = mfma32(lds_b128(Kh + swz(32 + r, 2 * (s & 3) + hh)), qf[s], S1);
+      }
+      // reg i <-> key kt*64 + t*32 + 8(i>>2) + 4hh + (i&3), as in the d64 kernel
+      const float* kbt = kbias_lds + buf * 64 + 4 * hh;
+      float mx = -INFINITY;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(kbt + 8 * g);
+        const f32x4 b1 = *reinterpret_cast<const f32x4*>(kbt + 32 + 8 * g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int i = 4 * g + j;
+          float x0 = fmaf(S0[i], a.scale_log2, b0[j]);
+          float x1 = fmaf(S1[i], a.scale_log2, b1[j]);
+          if (REL) {
+            const int ri = kt * 64 + 8 * g + 4 * hh + j - qi + a.rel_base;
+            x0 += relb_dyn[min(max(ri, 0), a.relb_len - 1)];
+            x1 += relb_dyn[min(max(ri + 32, 0), a.relb_len - 1)];
+          }
+          if (CAUSAL) {
+            const int key0 = kt * 64 + 8 * g + 4 * hh + j;
+            if (key0 > qi) x0 = -INFINITY;
+            if (key0 + 32 > qi) x1 = -INFINITY;
+          }
+          S0[i] = x0; S1[i] = x1;
+          mx = fmaxf(mx, fmaxf(x0, x1));
+        }
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m, mx);
+      const float msub = m_new == -INFINITY ? 0.f : m_new;
+      const float alpha = __builtin_amdgcn_exp2f(m - msub);
+      m = m_new;
+      float ps = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        S0[i] = __builtin_amdgcn_exp2f(S0[i] - msub);
+        S1[i] = __builtin_amdgcn_exp2f(S1[i] - msub);
+        ps += S0[i] + S1[i];
+      }
+      l = l * alpha + ps;
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) O[ob][i] *= alpha;
+      // P^T registers -> bf16 B fragments (k-step s2 of tile t = registers 8*s2 .. 8*s2+7)
+      bf16x8_t pf[2][2];
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          pf[0][s2][j] = (__bf16)S0[8 * s2 + j];
+          pf[1][s2][j] = (__bf16)S1[8 * s2 + j];
+        }
+      // O^T[d][q] += V^T[d][key] . P^T[key][q]; V^T fragments by transposed LDS reads
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const int kb = t * 32 + 16 * s2 + 4 * hh + trow;
+#pragma unroll
+          for (int ob = 0; ob < 4; ++ob) {
+            const char* Vh = Vb + (ob >> 1) * 8192;
+            const int col = 32 * (ob & 1) + tcol;
+            const bf16x8_t av = cat_tr(lds_tr(Vh + swz_e(kb, col)), lds_tr(Vh + swz_e(kb + 8, col)));
+            O[ob] = mfma32(av, pf[t][s2], O[ob]);
+          }
+        }
+    }
+    if (!resident) {
+      if (kt + 1 < nt && tid < 64) kbias_lds[(buf ^ 1) * 64 + tid] = stB;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+  }
+#undef FWD128_GLDS
+  if (!wactive) return;
+  l += __shfl_xor(l, 32, 64);
+  const float inv = l > 0.f ? 1.f / l : 0.f;
+  bf16_t* op = a.o + b * a.o_sb + h * a.o_sh + (long)(qvalid ? qi : 0) * a.o_ss;
+  store_row64(op, O[0], O[1], inv, hh, qvalid);
+  store_row64(op + 64, O[2], O[3], inv, hh, qvalid);
+  if (qvalid) {
+    if (hh == 0 && a.lse) a.lse[(long)bh * a.Sq + qi] = l > 0.f ? m + log2f(l) : INFINITY;
+  }
+}
+
 struct AttnBwdArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* dO; const bf16_t* o;
   long o_sb, o_ss, o_sh;
@@ -1108,6 +1325,45 @@ extern "C" int ct_attn_fwd_relbias(const void* q, const long* qs, const void* k,
   if (causal) attn_fwd_d64_kernel<false, true, true><<<grid, 256, 0, stream>>>(a);
   else attn_fwd_d64_kernel<false, false, true><<<grid, 256, 0, stream>>>(a);
   return 0;
+}
+
+// Head-dim-128 inference forward (attn_fwd_d128_kernel): the arguments of ct_attn_fwd without
+// dropout plus those of ct_attn_fwd_relbias; relb == nullptr selects the kernel without the
+// relative bias.  Rows are 128 elements, so the 32-bit offset check keeps 128 of slack.
+static inline bool fits32_d128(long rows, long row_stride) { return rows * row_stride + 128 < (1L << 31); }
+
+extern "C" int ct_attn_fwd_d128(const void* q, const long* qs, const void* k, const long* ks,
+                                const void* v, const long* vs, void* o, const long* os,
+                                const float* kbias, long kb_sb, const float* relb, long relb_sh,
+                                int relb_len, int rel_base, float* lse, int B, int H, int Sq, int Sk,
+                                float scale, int causal, hipStream_t stream) {
+  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || (relb && relb_len <= 0)) return -1;
+  if (relb && relb_len > kRelBiasMax) return -4;
+  if (!fits32_d128(Sq, qs[1]) || !fits32_d128(Sk, ks[1]) || !fits32_d128(Sk, vs[1]) || !fits32_d128(Sq, os[1]))
+    return -5;
+  if (((uintptr_t)o & 15) || os[0] % 8 || os[1] % 8 || os[2] % 8) return -7;   // 16-byte output stores
+  AttnFwdArgs a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
+  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
+  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
+  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
+  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
+  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse;
+  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  a.thr16 = 0; a.inv_keep = 1.f; a.hash_base = 0;
+  a.causal = causal;
+  a.relb = relb; a.relb_sh = relb ? relb_sh : 0; a.relb_len = relb ? relb_len : 0; a.rel_base = relb ? rel_base : 0;
+  dim3 grid((Sq + 127) / 128, B * H);
+  if (relb) {
+    const size_t dyn = (size_t)relb_len * sizeof(float);   // the relative-bias stage
+    if (causal) attn_fwd_d128_kernel<true, true><<<grid, 256, dyn, stream>>>(a);
+    else attn_fwd_d128_kernel<false, true><<<grid, 256, dyn, stream>>>(a);
+  } else {
+    if (causal) attn_fwd_d128_kernel<true, false><<<grid, 256, 0, stream>>>(a);
+    else attn_fwd_d128_kernel<false, false><<<grid, 256, 0, stream>>>(a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -8;
 }
 
 // delta workspace: float[B*H*Sq]; dq_acc workspace: float[B*H*Sq*64] zeroed (only used

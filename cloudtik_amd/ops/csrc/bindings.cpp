@@ -72,6 +72,9 @@ int ct_attn_fwd(const void*, const long*, const void*, const long*, const void*,
 int ct_attn_fwd_relbias(const void*, const long*, const void*, const long*, const void*, const long*, void*,
                         const long*, const float*, long, const float*, long, int, int, float*, int, int, int, int,
                         float, int, hipStream_t);
+int ct_attn_fwd_d128(const void*, const long*, const void*, const long*, const void*, const long*, void*,
+                     const long*, const float*, long, const float*, long, int, int, float*, int, int, int, int,
+                     float, int, hipStream_t);
 int ct_attn_bwd(const void*, const long*, const void*, const long*, const void*, const long*,
                 const void*, const long*, const void*, const long*, void*, const long*, void*,
                 const long*, void*, const long*, const float*, long, const float*, float*, float*,
@@ -405,20 +408,36 @@ std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor dlogits, int64_t 
   return {loss, lse};
 }
 
-// ---------------------------------------------------------------- attention (head_dim 64)
-// q, k, v, o: 4-D [B, S, H, 64] views with unit stride on the last dim (e.g. slices of a
-// packed [B, S, 3, H, 64] QKV projection output); key_bias: fp32 [B, Sk] additive.
-static void bshd_strides(const at::Tensor& t, long* st, const char* name) {
-  TORCH_CHECK(t.dim() == 4 && t.size(3) == 64 && t.stride(3) == 1, name, " must be [B,S,H,64] with unit last stride");
+// ---------------------------------------------------------------- attention (head_dim 64 / 128)
+// q, k, v, o: 4-D [B, S, H, D] views with unit stride on the last dim (e.g. slices of a
+// packed [B, S, 3, H, D] QKV projection output); key_bias: fp32 [B, Sk] additive.
+// The forward takes D = 64 or D = 128 (the d128 kernel: inference only); the backward D = 64.
+static void bshd_strides_fwd(const at::Tensor& t, long* st, const char* name) {
+  TORCH_CHECK(t.dim() == 4 && (t.size(3) == 64 || t.size(3) == 128) && t.stride(3) == 1, name,
+              " must be [B,S,H,64] or [B,S,H,128] with unit last stride");
   CHECK_CUDA(t); CHECK_BF16(t);
   st[0] = t.stride(0); st[1] = t.stride(1); st[2] = t.stride(2);
+}
+static void bshd_strides_bwd(const at::Tensor& t, long* st, const char* name) {
+  TORCH_CHECK(t.dim() == 4 && t.size(3) == 64 && t.stride(3) == 1, name,
+              " must be [B,S,H,64] with unit last stride (the head-dim-128 kernel is forward only)");
+  CHECK_CUDA(t); CHECK_BF16(t);
+  st[0] = t.stride(0); st[1] = t.stride(1); st[2] = t.stride(2);
+}
+// the head dim the forward dispatches on: q, k, v and o must agree
+static int fwd_head_dim(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o) {
+  const long D = q.size(3);
+  TORCH_CHECK(k.size(3) == D && v.size(3) == D && o.size(3) == D, "q, k, v and o must have the same head dim, got ",
+              D, ", ", k.size(3), ", ", v.size(3), ", ", o.size(3));
+  return (int)D;
 }
 
 at::Tensor attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                     c10::optional<at::Tensor> key_bias, double scale, double p, int64_t seed,
                     int64_t offset, bool causal) {
   long qs[3], ks[3], vs[3], os[3];
-  bshd_strides(q, qs, "q"); bshd_strides(k, ks, "k"); bshd_strides(v, vs, "v"); bshd_strides(o, os, "o");
+  bshd_strides_fwd(q, qs, "q"); bshd_strides_fwd(k, ks, "k"); bshd_strides_fwd(v, vs, "v"); bshd_strides_fwd(o, os, "o");
+  const int D = fwd_head_dim(q, k, v, o);
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
   TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
   TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
@@ -429,6 +448,14 @@ at::Tensor attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
     kb = key_bias->data_ptr<float>(); kb_sb = key_bias->stride(0);
   }
   auto lse = at::empty({(long)B * H, Sq}, q.options().dtype(at::kFloat));
+  if (D == 128) {
+    TORCH_CHECK(p == 0.0, "attn_fwd: the head-dim-128 kernel has no dropout (p must be 0)");
+    int rc = ct_attn_fwd_d128(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
+                              nullptr, 0, 0, 0, lse.data_ptr<float>(), B, H, Sq, Sk, (float)scale, causal ? 1 : 0,
+                              cur_stream());
+    TORCH_CHECK(rc == 0, "attn_fwd (head dim 128) failed rc=", rc);
+    return lse;
+  }
   int rc = ct_attn_fwd(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
                        lse.data_ptr<float>(), B, H, Sq, Sk, (float)scale, (float)p, (uint64_t)seed,
                        (uint64_t)offset, causal ? 1 : 0, cur_stream());
@@ -441,7 +468,8 @@ at::Tensor attn_fwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor
                             c10::optional<at::Tensor> key_bias, at::Tensor relb, int64_t rel_base, double scale,
                             bool causal) {
   long qs[3], ks[3], vs[3], os[3];
-  bshd_strides(q, qs, "q"); bshd_strides(k, ks, "k"); bshd_strides(v, vs, "v"); bshd_strides(o, os, "o");
+  bshd_strides_fwd(q, qs, "q"); bshd_strides_fwd(k, ks, "k"); bshd_strides_fwd(v, vs, "v"); bshd_strides_fwd(o, os, "o");
+  const int D = fwd_head_dim(q, k, v, o);
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
   TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
   TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
@@ -457,6 +485,13 @@ at::Tensor attn_fwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor
     kb = key_bias->data_ptr<float>(); kb_sb = key_bias->stride(0);
   }
   auto lse = at::empty({(long)B * H, Sq}, q.options().dtype(at::kFloat));
+  if (D == 128) {
+    int rc = ct_attn_fwd_d128(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
+                              relb.data_ptr<float>(), relb.stride(0), (int)L, (int)rel_base, lse.data_ptr<float>(),
+                              B, H, Sq, Sk, (float)scale, causal ? 1 : 0, cur_stream());
+    TORCH_CHECK(rc == 0, "attn_fwd_relbias (head dim 128) failed rc=", rc);
+    return lse;
+  }
   int rc = ct_attn_fwd_relbias(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
                                relb.data_ptr<float>(), relb.stride(0), (int)L, (int)rel_base, lse.data_ptr<float>(),
                                B, H, Sq, Sk, (float)scale, causal ? 1 : 0, cur_stream());
@@ -468,8 +503,8 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
               at::Tensor dk, at::Tensor dv, c10::optional<at::Tensor> key_bias, at::Tensor lse,
               double scale, double p, int64_t seed, int64_t offset, bool causal) {
   long qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
-  bshd_strides(q, qs, "q"); bshd_strides(k, ks, "k"); bshd_strides(v, vs, "v"); bshd_strides(o, os, "o");
-  bshd_strides(dO, dos, "dO"); bshd_strides(dq, dqs, "dq"); bshd_strides(dk, dks, "dk"); bshd_strides(dv, dvs, "dv");
+  bshd_strides_bwd(q, qs, "q"); bshd_strides_bwd(k, ks, "k"); bshd_strides_bwd(v, vs, "v"); bshd_strides_bwd(o, os, "o");
+  bshd_strides_bwd(dO, dos, "dO"); bshd_strides_bwd(dq, dqs, "dq"); bshd_strides_bwd(dk, dks, "dk"); bshd_strides_bwd(dv, dvs, "dv");
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
   TORCH_CHECK(dO.sizes() == o.sizes() && dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes());
   TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);

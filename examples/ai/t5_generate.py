@@ -31,11 +31,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 
+_SIZES = {"3b": "xl", "11b": "xxl"}         # --size name -> T5Config constructor
+
+
 def load_model(checkpoint, size, device, dtype):
     from cloudtik_amd.models.t5 import T5Config, T5ForConditionalGeneration
     if checkpoint is None:
         torch.manual_seed(0)
-        return T5ForConditionalGeneration(getattr(T5Config, size)(dropout_rate=0.0), device=device, dtype=dtype).eval()
+        return T5ForConditionalGeneration(getattr(T5Config, _SIZES.get(size, size))(dropout_rate=0.0), device=device, dtype=dtype).eval()
     model = T5ForConditionalGeneration.from_hf_config(os.path.join(checkpoint, "config.json"), device=device, dtype=dtype)
     for name in ("model.safetensors", "pytorch_model.bin"):
         path = os.path.join(checkpoint, name)
@@ -58,7 +61,7 @@ def load_tokenizer(checkpoint):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint", default=None, help="local directory with config.json and the weights")
-    ap.add_argument("--size", default="small", choices=["tiny", "small", "base", "large"], help="random-init topology")
+    ap.add_argument("--size", default="small", choices=["tiny", "small", "base", "large", "3b", "11b"], help="random-init topology")
     ap.add_argument("--text", action="append", help="source sentence (repeatable; needs the tokenizer)")
     ap.add_argument("--batch", type=int, default=2, help="random sources when there is no text")
     ap.add_argument("--source-len", type=int, default=24)
