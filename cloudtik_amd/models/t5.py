@@ -10,9 +10,10 @@ bucketed relative-position bias shared by all layers of a stack, ReLU (v1.0) or 
 MI355X mapping: RMS norms run in the HIP LayerNorm kernel (``rms=True``); the relative
 position bias is carried as one [H, Sq + Sk - 1] vector per stack (bias depends only on
 key - query) and added inside the MFMA flash-attention kernel (``ops.attention_relbias``),
-so inference never materialises an [H, Sq, Sk] bias; cross-attention uses the MFMA kernel
-with the per-key padding mask; training self-attention (which needs the bias gradient) uses
-SDPA with the gathered bias, as does every attention that needs a gradient at d_kv = 128 (the
+so neither inference nor d_kv-64 training materialises an [H, Sq, Sk] bias: the kernels'
+backward returns the gradient of that vector (not bitwise reproducible: fp32 LDS adds) and both
+directions take attention dropout; cross-attention uses the MFMA kernel with the per-key padding
+mask; every attention that needs a gradient at d_kv = 128 uses SDPA with the gathered bias (the
 head-dim-128 kernel is forward only); the training loss is the fused linear + cross-entropy HIP
 kernel over the 32128-token vocabulary; generation keeps a per-layer KV cache and replays
 the decode step as a HIP graph, greedy, with beam search (``ops/beam.py``, ``csrc/beam.hip``) or
@@ -138,6 +139,13 @@ def relative_position_bucket(rel: torch.Tensor, bidirectional: bool, num_buckets
     return ret + torch.where(small, n, large)
 
 
+def train_attention_kernels() -> bool:
+    """Whether d_kv-64 attention takes the HIP kernels in grad mode and under dropout (default);
+    ``CLOUDTIK_AMD_T5_TRAIN_ATTN=0`` keeps those calls on ``F.scaled_dot_product_attention`` with
+    a materialised bias, the earlier routing (the A/B switch of bench/t5_train_probe.py)."""
+    return os.environ.get("CLOUDTIK_AMD_T5_TRAIN_ATTN", "1") != "0"
+
+
 class T5Norm(nn.Module):
     def __init__(self, d, eps, device=None, dtype=None):
         super().__init__()
@@ -210,11 +218,16 @@ class T5Attention(nn.Module):
         # causal masking in the kernel is top-left aligned: exact for prefill (offset 0) and for
         # single-token decode steps (every cached key is visible)
         causal = self.causal and S > 1
-        if rel is not None and kernel_ok and not grad and (offset == 0 or not causal):
+        # d_kv 64 trains on the kernels: self-attention with the bias gradient and dropout
+        # (ops.attention_relbias), cross-attention with dropout (ops.attention).
+        # CLOUDTIK_AMD_T5_TRAIN_ATTN=0 sends grad-mode and dropout calls back to SDPA below.
+        train_kernels = self.dk == 64 and train_attention_kernels()
+        p = self.cfg.dropout_rate if (self.training and train_kernels) else 0.0
+        if rel is not None and kernel_ok and (train_kernels or not grad) and (offset == 0 or not causal):
             relvec, rel_base = rel
-            o = ops.attention_relbias(q, k, v, relvec, rel_base, key_bias, scale=1.0, causal=causal)
-        elif rel is None and kernel_ok and not (self.training and self.cfg.dropout_rate):
-            o = ops.attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), key_bias=key_bias,
+            o = ops.attention_relbias(q, k, v, relvec, rel_base, key_bias, scale=1.0, causal=causal, p=p)
+        elif rel is None and kernel_ok and (train_kernels or not (self.training and self.cfg.dropout_rate)):
+            o = ops.attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), key_bias=key_bias, p=p,
                               scale=1.0, causal=causal).transpose(1, 2)          # T5 folds the scale into init
         else:
             bias = None

@@ -130,20 +130,43 @@ def attention(q, k, v, key_bias=None, p=0.0, scale=None, causal=False):
     return ref.attention(q, k, v, key_bias, p, seed, offset, scale, causal)
 
 
-def attention_relbias(q, k, v, rel_bias, rel_base: int, key_bias=None, scale: float = 1.0, causal: bool = False):
-    """Inference attention with a relative-position bias (T5): q/k/v ``[B, S, H, D]``,
-    ``rel_bias [H, L]`` adds ``rel_bias[h, k - q + rel_base]`` to every score (natural-log
-    units), ``key_bias [B, Sk]`` masks keys.  HIP MFMA kernel on the GPU (bf16, D = 64 or 128);
-    fp32 PyTorch reference elsewhere.  Forward only."""
+
+
+class _AttnRelFn(torch.autograd.Function):
+    """Relative-bias attention at head dim 64: attn_fwd_relbias_train / attn_bwd_relbias."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_bias, key_bias, rel_base, scale, p, seed, offset, causal):
+        # q, k, v: [B, S, H, 64]; rel_bias: [H, L] in any layout and dtype
+        relc = rel_bias.detach().float().contiguous()
+        o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        lse = _ops().require_native().attn_fwd_relbias_train(q, k, v, o, key_bias, relc, rel_base, scale, p, seed,
+                                                             offset, causal)
+        ctx.save_for_backward(q, k, v, o, lse, relc, rel_bias, key_bias if key_bias is not None else torch.empty(0))
+        ctx.cfg = (rel_base, scale, p, seed, offset, causal, key_bias is not None)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, relc, rel_bias, kb = ctx.saved_tensors
+        rel_base, scale, p, seed, offset, causal, has_kb = ctx.cfg
+        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        dk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
+        dv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
+        # the gradient in the layout of the bias that was passed (the T5 model passes the
+        # transpose of an [L, H] gather, so its backward gets a contiguous [L, H])
+        d_rel = torch.empty_like(rel_bias, dtype=torch.float32)
+        _ops().require_native().attn_bwd_relbias(q, k, v, o, do.contiguous(), dq, dk, dv, d_rel,
+                                                 kb if has_kb else None, relc, rel_base, lse, scale, p, seed, offset,
+                                                 causal)
+        return dq, dk, dv, d_rel.to(rel_bias.dtype), None, None, None, None, None, None, None
+
+
+def _relbias_reference(q, k, v, rel_bias, rel_base, key_bias, scale, causal, p, seed, offset):
+    """PyTorch fallback of attention_relbias: fp32, differentiable; p > 0 drops the elements the
+    kernels drop (ref.attn_dropout_keep)."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
-    if (q.is_cuda and q.dtype == torch.bfloat16 and D in (64, 128) and rel_bias.shape[1] <= 4096
-            and _ops().native_available()):
-        o = torch.empty_like(q)
-        kb = key_bias.float().contiguous() if key_bias is not None else None
-        _ops().require_native().attn_fwd_relbias(q, k, v, o, kb, rel_bias.float().contiguous(), int(rel_base),
-                                                 float(scale), bool(causal))
-        return o
     idx = (torch.arange(Sk, device=q.device)[None, :] - torch.arange(Sq, device=q.device)[:, None] + rel_base)
     bias = rel_bias.float()[:, idx.clamp(0, rel_bias.shape[1] - 1)][None]            # [1, H, Sq, Sk]
     if key_bias is not None:
@@ -151,4 +174,43 @@ def attention_relbias(q, k, v, rel_bias, rel_base: int, key_bias=None, scale: fl
     s = torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) * scale + bias
     if causal:
         s = s.masked_fill(torch.ones(Sq, Sk, dtype=torch.bool, device=q.device).triu(1), float("-inf"))
-    return torch.einsum("bhqk,bkhd->bqhd", torch.softmax(s, -1), v.float()).to(q.dtype)
+    pr = torch.softmax(s, -1)
+    if p > 0.0:
+        keep = ref.attn_dropout_keep(B, H, Sq, Sk, p, seed, offset).to(q.device)
+        pr = torch.where(keep, pr / (1.0 - p), torch.zeros_like(pr))
+    return torch.einsum("bhqk,bkhd->bqhd", pr, v.float()).to(q.dtype)
+
+
+def attention_relbias(q, k, v, rel_bias, rel_base: int, key_bias=None, scale: float = 1.0, causal: bool = False,
+                      p: float = 0.0):
+    """Attention with a relative-position bias (T5): q/k/v ``[B, S, H, D]``, ``rel_bias [H, L]``
+    adds ``rel_bias[h, k - q + rel_base]`` to every score (natural-log units), ``key_bias
+    [B, Sk]`` masks keys, ``p`` is attention-probability dropout (the stream of
+    :func:`attention`).  HIP MFMA kernels on the GPU in bf16: D = 64 trains (differentiable in
+    q, k, v and ``rel_bias``; the gradient of ``rel_bias`` sums fp32 dS with LDS float adds and is
+    not bitwise reproducible), D = 128 is forward only without dropout.  Everything else -- CPU
+    or fp32 tensors, D = 128 with a gradient or dropout, odd Sk with p > 0, L > 4096, a query
+    length whose backward windows do not fit the kernel's LDS budget -- takes the differentiable
+    PyTorch reference."""
+    B, Sq, H, D = q.shape
+    Sk = k.shape[1]
+    p = float(p)
+    ops = _ops()
+    seed, offset = ops._rng.next(B * H * Sq * Sk) if p > 0 else (0, 0)
+    native = (q.is_cuda and q.dtype == torch.bfloat16 and D in (64, 128) and rel_bias.shape[1] <= 4096
+              and ops.native_available())
+    grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad
+                                        or rel_bias.requires_grad)
+    if native and not grad and p == 0:
+        o = torch.empty_like(q)
+        kb = key_bias.float().contiguous() if key_bias is not None else None
+        ops.require_native().attn_fwd_relbias(q, k, v, o, kb, rel_bias.float().contiguous(), int(rel_base),
+                                              float(scale), bool(causal))
+        return o
+    if native and D == 64 and (p == 0 or Sk % 2 == 0):
+        C = ops.require_native()
+        if not grad or C.attn_bwd_relbias_window(Sq) <= C.attn_bwd_relbias_max_window():
+            kb = key_bias.float().contiguous() if key_bias is not None else None
+            return _AttnRelFn.apply(q, k, v, rel_bias, kb, int(rel_base), float(scale), p, seed, offset,
+                                    bool(causal))
+    return _relbias_reference(q, k, v, rel_bias, rel_base, key_bias, float(scale), causal, p, seed, offset)

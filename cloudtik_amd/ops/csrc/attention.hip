@@ -34,6 +34,9 @@
 //     keys (S <= 128, the BERT phase-1 case), otherwise accumulated with fp32 atomics and
 //     converted by a tiny kernel.
 //   * attention-prob dropout regenerated from a counter hash (nothing stored).
+//   * the kernel body is attention_bwd_d64_body.h, included by attn_bwd_d64_kernel and by
+//     attn_bwd_d64_rel_kernel (T5 training: relative-position bias in the score, its gradient
+//     out through LDS float adds and attn_drel_reduce_kernel; notes in front of the kernels).
 // Head dim 128 (attn_fwd_d128_kernel<CAUSAL, REL>): the forward above with 8 k-steps for S^T and
 // four O^T blocks; a K/V tile is two 64-column halves in the d64 LDS image; K/V by
 // global_load_lds into a two-deep ring; the relative-bias stage is dynamic LDS sized to the
@@ -813,6 +816,10 @@ struct AttnBwdArgs {
   int B, H, Sq, Sk;
   float scale_log2, scale;
   uint32_t thr16; float inv_keep; uint32_t hash_base; int causal;
+  // the relative-bias backward only (REL): score(q, k) += relb[h][k - q + rel_base] (natural-log
+  // units); drel_ws [B, nkb, H, W] fp32 takes each workgroup's window of the bias gradient
+  const float* relb; long relb_sh; int relb_len; int rel_base;
+  float* drel_ws;
 };
 
 // GL (single key block and Sq <= 128 only): every LDS tile arrives by global_load_lds -- K, V
@@ -822,349 +829,50 @@ struct AttnBwdArgs {
 // (the register-staged form gives half a tile and stalls on it: 47 % of wave cycles parked in
 // s_waitcnt / barrier).  lse and delta = rowsum(dO * O) are computed for all (<= 128) rows
 // once in the prologue instead of per tile, so the loop issues no register-destined loads.
+//
+// REL (relative-position bias, T5 training): the score gets rel[h][key - query + rel_base] and the
+// kernel also produces the gradient of that vector.  A workgroup owns keys k0 .. k0 + 127 and
+// walks query rows 0 .. 32 nq - 1, so the offsets it touches form ONE window of
+// W = 32 nq + 127 entries starting at win0 = k0 - (32 nq - 1) + rel_base; window index
+// (key - k0) - query + 32 nq - 1 lies in [0, W) for every (query, key) of the padded tiles, rows
+// past Sq and keys past Sk included, so no LDS address can leave the window.  Two windows of
+// dynamic LDS (sized at launch): the bias, log2-scaled, zero where win0 + i is outside [0, L)
+// (only padded rows / keys land there, and their P is 0), and the fp32 sum of dS per offset.
+// dS is taken in fp32 before its bf16 rounding and added with LDS float adds (in register i
+// consecutive lanes hold consecutive keys: consecutive addresses per 32-lane half).  The window
+// is then stored whole, with plain stores, into a [B, nkb, H, W] workspace that
+// attn_drel_reduce_kernel sums in a fixed order.  The LDS adds of one workgroup land in an
+// order the hardware picks, so d_rel is NOT bitwise reproducible from run to run (the sum
+// across workgroups is).  REL has no GL form: Sq <= 128 runs the register-staged kernel.
+// The REL kernels have a name of their own, attn_bwd_d64_rel_kernel<DROP, CAUSAL, MULTI>, so
+// that attn_bwd_d64_kernel<DROP, CAUSAL, MULTI, GL> keeps the name tests and profiles match on;
+// both include the one body (attention_bwd_d64_body.h) with REL as a compile-time constant.
 template <bool DROP, bool CAUSAL, bool MULTI, bool GL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_d64_kernel(AttnBwdArgs a) {
-  // LDS: Q tiles R x 4K | dO tiles R x 4K | K block 16K | V block 16K | dS^T 2 x 8K | lse, delta
-  // (R = 2 register-staged: 2 x 32 rows each; R = 3 with GL: all <= 128 rows each)
-  // The per-q-tile inputs (Q, dO, lse, delta) and dS^T are multi-buffered, so one barrier per
-  // q-tile orders everything: tile t+2 is staged into the buffers tile t (t - 1 with GL) has
-  // released, and dQ needs no cross-wave reduction (each wave owns 16 queries x 32 d of the
-  // tile's dQ and sums over all 128 keys itself).
-  static_assert(!(GL && MULTI), "GL: single key block only");
-  constexpr int QR = GL ? 3 : 2;
-  constexpr int QB = QR * 4096;
-  __shared__ __attribute__((aligned(16))) char smem[2 * QB + 16384 + 16384 + 16384 + (GL ? 1024 : 512)];
-  char* Qs = smem;
-  char* dOs = smem + QB;
-  char* Ks = smem + 2 * QB;
-  char* Vs = Ks + 16384;
-  char* dSs = Vs + 16384;
-  float* lse_s = reinterpret_cast<float*>(dSs + 16384);       // [2][32] or [128]
-  float* delta_s = lse_s + (GL ? 128 : 64);                   // [2][32] or [128]
+  constexpr bool REL = false;
+#include "attention_bwd_d64_body.h"
+}
 
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hh = lane >> 5;
-  const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
-  const int k0 = blockIdx.x * 128;
-  const int key_l = k0 + w * 32 + r;  // this lane's key (MFMA column)
-  const bool kvalid = key_l < a.Sk;
-  const float LOG2E = 1.4426950408889634f;
+template <bool DROP, bool CAUSAL, bool MULTI>
+__global__ __launch_bounds__(256, 2) void attn_bwd_d64_rel_kernel(AttnBwdArgs a) {
+  constexpr bool GL = false, REL = true;
+#include "attention_bwd_d64_body.h"
+}
 
-  const bf16_t* kp = a.k + b * a.k_sb + h * a.k_sh;
-  const bf16_t* vp = a.v + b * a.v_sb + h * a.v_sh;
-  // K and V blocks (128 keys) into LDS: row reads give the B operands of S = Q K^T and
-  // dP = dO V^T (re-read per q-tile instead of pinning 32 VGPRs), transposed reads of K
-  // give dQ's operand
-  if constexpr (GL) {
-    // wave w DMAs rows 32 w + 8 i + (lane >> 3); lane l lands at physical chunk l & 7, so it
-    // fetches logical chunk (l & 7) ^ rev3(((row >> 1) & 7)) = (l & 7) ^ rev3((4 i + (l >> 4)) & 7).
-    // Rows past Sk read row Sk - 1 (finite; their -inf key bias zeroes them)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 32 * w + 8 * i + (lane >> 3);
-      const unsigned key = (unsigned)min(k0 + row, a.Sk - 1);
-      const unsigned c = (unsigned)((lane & 7) ^ rev3((4 * i + (lane >> 4)) & 7));
-      at_glds16s(kp, (key * (unsigned)a.k_ss + c * 8u) * 2u, Ks + (32 * w + 8 * i) * 128);
-      at_glds16s(vp, (key * (unsigned)a.v_ss + c * 8u) * 2u, Vs + (32 * w + 8 * i) * 128);
+// d_rel[h][i] (fp32, strided) = the sum over (batch, key block), in that fixed order, of the
+// workspace windows that hold offset i; every entry is written, an offset in no window as 0.
+__global__ void attn_drel_reduce_kernel(const float* __restrict__ ws, float* __restrict__ drel, long d_sh, long d_si,
+                                        int B, int nkb, int H, int W, int L, int win00) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= H * L) return;
+  const int h = t / L, i = t - h * L;
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b)
+    for (int kb = 0; kb < nkb; ++kb) {
+      const int li = i - (win00 + 128 * kb);       // window of key block kb starts at win00 + 128 kb
+      if (li >= 0 && li < W) acc += ws[(((long)b * nkb + kb) * H + h) * W + li];
     }
-  } else {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = tid + 256 * i;
-    const int row = c >> 3, ch = c & 7;
-    const int key = k0 + row;
-    const bool ok = key < a.Sk;
-    const u16x8 kv = ok ? *reinterpret_cast<const u16x8*>(kp + (long)key * a.k_ss + ch * 8) : u16x8(0);
-    const u16x8 vv = ok ? *reinterpret_cast<const u16x8*>(vp + (long)key * a.v_ss + ch * 8) : u16x8(0);
-    *reinterpret_cast<u16x8*>(Ks + swz(row, ch)) = kv;
-    *reinterpret_cast<u16x8*>(Vs + swz(row, ch)) = vv;
-  }
-  }
-  const int krow = w * 32 + r;   // this lane's key row inside the block
-  float kb2 = 0.f;
-  if (a.kbias && kvalid) kb2 = a.kbias[b * a.kb_sb + key_l] * LOG2E;
-  if (!kvalid) kb2 = -INFINITY;
-
-  f32x16 dV0, dV1, dK0, dK1;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { dV0[i] = 0.f; dV1[i] = 0.f; dK0[i] = 0.f; dK1[i] = 0.f; }
-
-  const bf16_t* qbase = a.q + b * a.q_sb + h * a.q_sh;
-  const bf16_t* dobase = a.dO + b * a.do_sb + h * a.do_sh;
-  const bf16_t* obase = a.o + b * a.o_sb + h * a.o_sh;
-  bf16_t* dqbase = a.dq + b * a.dq_sb + h * a.dq_sh;
-  const int trow = (lane >> 2) & 3;
-  const int tcol = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
-  const int nq = (a.Sq + 31) / 32;
-  // MULTI: Sk > 128, several key blocks per (batch, head) -> dQ summed by fp32 atomics
-  constexpr bool single_block = !MULTI;
-  // 16-byte dQ stores need 8-element strides and a 16-byte aligned base
-  const bool dq16 = ((a.dq_ss | a.dq_sb | a.dq_sh) & 7) == 0 && (((uintptr_t)a.dq) & 15) == 0;
-  // this wave's share of the tile's dQ: queries 16 (w & 1) .. +16, d 32 (w >> 1) .. +32
-  const int dq_q0 = 16 * (w & 1), dq_d0 = 32 * (w >> 1);
-  // 16x16x32 fragment lane roles (transposing reads): g = lane >> 4 picks 8 keys, q4 / p4 a
-  // row / 4-column group inside them
-  const int fg = lane >> 4, fq = (lane & 15) >> 2, fp = lane & 3;
-
-  // Q / dO / lse / delta tiles are register-prefetched two q-tiles ahead (issued before the
-  // tile's MFMAs, written to LDS after its barrier into the buffer it has just released)
-  const int prow = tid >> 3, pch = tid & 7;
-  // delta = rowsum(dO * O) is computed here (no separate kernel): each thread prefetches
-  // the O chunk matching its dO chunk; the 8 threads of a row reduce at staging time
-  u16x8 pQ, pdO, pO;
-  float pL = INFINITY;
-#define BWD_PREFETCH(qb_)                                                                   \
-  {                                                                                         \
-    const int q_ = (qb_) + prow;                                                            \
-    const bool ok_ = q_ < a.Sq;                                                             \
-    pQ = ok_ ? *reinterpret_cast<const u16x8*>(qbase + (q_ * (int)a.q_ss + pch * 8)) : u16x8(0); \
-    pdO = ok_ ? *reinterpret_cast<const u16x8*>(dobase + (q_ * (int)a.do_ss + pch * 8)) : u16x8(0); \
-    pO = ok_ ? *reinterpret_cast<const u16x8*>(obase + (q_ * (int)a.o_ss + pch * 8)) : u16x8(0); \
-    if (tid < 32) {                                                                         \
-      const bool ok2_ = (qb_) + tid < a.Sq;                                                 \
-      pL = ok2_ ? a.lse[(long)bh * a.Sq + (qb_) + tid] : INFINITY;                          \
-    }                                                                                       \
-  }
-#define BWD_STAGE(buf_)                                                                     \
-  {                                                                                         \
-    *reinterpret_cast<u16x8*>(Qs + (buf_) * 4096 + swz(prow, pch)) = pQ;                    \
-    *reinterpret_cast<u16x8*>(dOs + (buf_) * 4096 + swz(prow, pch)) = pdO;                  \
-    if (tid < 32) lse_s[(buf_) * 32 + tid] = pL;                                            \
-    float dd_ = 0.f;                                                                        \
-    _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) dd_ += bf2f(pdO[j_]) * bf2f(pO[j_]);  \
-    dd_ += __shfl_xor(dd_, 1, 64);                                                          \
-    dd_ += __shfl_xor(dd_, 2, 64);                                                          \
-    dd_ += __shfl_xor(dd_, 4, 64);                                                          \
-    if (pch == 0) delta_s[(buf_) * 32 + prow] = dd_;                                        \
-  }
-  // GL: Q / dO tile t (32 rows) into ring slot `slot_`: wave w DMAs rows 8 w + (lane >> 3) of
-  // each (one 1 KB instruction per operand); rows past Sq read row Sq - 1 (finite; their
-  // +inf lse zeroes every product they enter)
-#define BWD_GLDS(qb_, slot_)                                                                \
-  {                                                                                         \
-    const unsigned q_ = (unsigned)min((qb_) + 8 * w + (lane >> 3), a.Sq - 1);               \
-    const unsigned c_ = (unsigned)((lane & 7) ^ rev3((4 * w + (lane >> 4)) & 7));           \
-    at_glds16s(qbase, (q_ * (unsigned)a.q_ss + c_ * 8u) * 2u, Qs + (slot_) * 4096 + w * 1024); \
-    at_glds16s(dobase, (q_ * (unsigned)a.do_ss + c_ * 8u) * 2u, dOs + (slot_) * 4096 + w * 1024); \
-  }
-  if constexpr (GL) {
-    BWD_GLDS(0, 0);
-    if (nq > 1) BWD_GLDS(32, 1);
-    // lse and delta of all rows: thread (row tid >> 1, half tid & 1) dots 32 d of dO and O
-    {
-      const int row = tid >> 1, hf = tid & 1;
-      float dd = 0.f;
-      if (row < a.Sq) {
-        const bf16_t* dr = dobase + row * (int)a.do_ss + 32 * hf;
-        const bf16_t* orow = obase + row * (int)a.o_ss + 32 * hf;
-        u16x8 dv[4], ov[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          dv[j] = *reinterpret_cast<const u16x8*>(dr + 8 * j);
-          ov[j] = *reinterpret_cast<const u16x8*>(orow + 8 * j);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) dd += bf2f(dv[j][e]) * bf2f(ov[j][e]);
-      }
-      dd += __shfl_xor(dd, 1, 64);
-      if (hf == 0 && row < 128) delta_s[row] = dd;
-      if (tid < 128) lse_s[tid] = tid < a.Sq ? a.lse[(long)bh * a.Sq + tid] : INFINITY;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-  BWD_PREFETCH(0);
-  BWD_STAGE(0);
-  if (nq > 1) {
-    BWD_PREFETCH(32);
-    BWD_STAGE(1);
-  }
-  }
-  __syncthreads();
-
-  int slot = 0;      // GL: ring slot of tile qt
-  for (int qt = 0; qt < nq; ++qt) {
-    const int qb = qt * 32;
-    const int buf = qt & 1;
-    if constexpr (GL) {
-      // slot of tile qt + 2 == slot of tile qt - 1 (released at tile qt - 1's barrier)
-      if (qt + 2 < nq) { const int s2 = slot == 0 ? 2 : slot - 1; BWD_GLDS(qb + 64, s2); }
-    } else {
-      if (qt + 2 < nq) BWD_PREFETCH(qb + 64);
-    }
-    const char* Qt = Qs + (GL ? slot : buf) * 4096;
-    const char* dOt = dOs + (GL ? slot : buf) * 4096;
-    const float* lse_t = lse_s + (GL ? qb : buf * 32);
-    const float* delta_t = delta_s + (GL ? qb : buf * 32);
-    char* dSt = dSs + buf * 8192;
-    f32x16 S, dP;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { S[i] = 0.f; dP[i] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      S = mfma32(lds_b128(Qt + swz(r, 2 * s + hh)), lds_b128(Ks + swz(krow, 2 * s + hh)), S);
-      dP = mfma32(lds_b128(dOt + swz(r, 2 * s + hh)), lds_b128(Vs + swz(krow, 2 * s + hh)), dP);
-    }
-    // dropout keep bits: the pair (even key, odd key) shares one hash; the two lanes of a
-    // pair (lane ^ 1) each hash 8 of the 16 query rows and swap halves with one DPP move
-    // packed into one register: bit i = keep decision of register i
-    uint32_t keepbits = 0xFFFFu;
-    if (DROP) {
-      const uint32_t T0 = (uint32_t)(((uint64_t)bh * a.Sq + qb) * (uint64_t)(a.Sk >> 1));
-      const uint32_t half_sk = (uint32_t)(a.Sk >> 1);
-      const int hsel = r & 1;                // == key_l & 1 (k0, w*32 even)
-      uint32_t mine = 0, theirs = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = 8 * hsel + j;
-        const int qrow = (i & 3) + 8 * (i >> 2) + 4 * hh;
-        const uint32_t rr = hash_u32((T0 + (uint32_t)qrow * half_sk + (uint32_t)(key_l >> 1)) ^ a.hash_base);
-        const uint32_t klo = (rr & 0xFFFFu) >= a.thr16, khi = (rr >> 16) >= a.thr16;
-        mine |= (hsel ? khi : klo) << i;
-        theirs |= (hsel ? klo : khi) << i;
-      }
-      keepbits = mine | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)theirs, 0xB1, 0xF, 0xF, false);
-    }
-    // reg i <-> query row qrow(i) = (i&3) + 8(i>>2) + 4hh of this tile; column = key_l
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 L4 = *reinterpret_cast<const f32x4*>(lse_t + 8 * g + 4 * hh);
-      const f32x4 D4 = *reinterpret_cast<const f32x4*>(delta_t + 8 * g + 4 * hh);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = 4 * g + j;
-        float x = fmaf(S[i], a.scale_log2, kb2);
-        if (CAUSAL && key_l > qb + 8 * g + 4 * hh + j) x = -INFINITY;
-        const float p = __builtin_amdgcn_exp2f(x - L4[j]);
-        float pd = p, dpv = dP[i];
-        if (DROP) {
-          const bool keep = (keepbits >> i) & 1u;
-          pd = keep ? p * a.inv_keep : 0.f;
-          dpv = keep ? dpv * a.inv_keep : 0.f;
-        }
-        S[i] = pd;                        // P (after dropout) for dV
-        dP[i] = p * (dpv - D4[j]);        // dS (unscaled) for dK, dQ
-      }
-    }
-    bf16x8_t pf[2], dsf[2];
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { pf[s2][j] = (__bf16)S[8 * s2 + j]; dsf[s2][j] = (__bf16)dP[8 * s2 + j]; }
-    // dV^T += dO^T . P ; dK^T += Q^T . dS   (A operands by transposed reads of the tiles)
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const int qr = 16 * s2 + 4 * hh + trow;
-      const bf16x8_t ado0 = cat_tr(lds_tr(dOt + swz_e(qr, tcol)), lds_tr(dOt + swz_e(qr + 8, tcol)));
-      const bf16x8_t ado1 = cat_tr(lds_tr(dOt + swz_e(qr, 32 + tcol)), lds_tr(dOt + swz_e(qr + 8, 32 + tcol)));
-      const bf16x8_t aq0 = cat_tr(lds_tr(Qt + swz_e(qr, tcol)), lds_tr(Qt + swz_e(qr + 8, tcol)));
-      const bf16x8_t aq1 = cat_tr(lds_tr(Qt + swz_e(qr, 32 + tcol)), lds_tr(Qt + swz_e(qr + 8, 32 + tcol)));
-      dV0 = mfma32(ado0, pf[s2], dV0);
-      dV1 = mfma32(ado1, pf[s2], dV1);
-      dK0 = mfma32(aq0, dsf[s2], dK0);
-      dK1 = mfma32(aq1, dsf[s2], dK1);
-    }
-    // dS^T -> LDS [128 keys][32 q] (64-byte rows, 8-byte chunks XOR dsw(key), below):
-    // each lane owns one key row and 4 runs of 4 consecutive queries -> 4 ds_write_b64
-    {
-      const int key = w * 32 + r;
-      char* rowp = dSt + key * 64;
-      const int sw = dsw(key);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c = 2 * g + hh;     // 8-byte chunk = queries 8g + 4hh .. +3
-        u16x4 v = {f2bf(dP[4 * g]), f2bf(dP[4 * g + 1]), f2bf(dP[4 * g + 2]), f2bf(dP[4 * g + 3])};
-        *reinterpret_cast<u16x4*>(rowp + ((c ^ sw) << 3)) = v;
-      }
-    }
-    if constexpr (GL) {
-      // tile qt + 1's DMA (issued a tile and a half ago) must have landed before this barrier;
-      // only tile qt + 2's two pieces may stay in flight
-      if (qt + 2 < nq) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      slot = slot == 2 ? 0 : slot + 1;
-    }
-    __syncthreads();   // the ONLY barrier of the tile: dS^T complete; this tile's Q / dO / lse /
-                       // delta buffers free; tile t+1's staged buffers visible
-    // tile qt + 2's inputs into the buffers tile qt released at this barrier (staging after the
-    // dQ stores instead measured slower: its vmcnt wait then covers those stores too)
-    if constexpr (!GL) {
-      if (qt + 2 < nq) BWD_STAGE(buf);
-    }
-    // dQ[q][d] = sum over the 128 keys of dS[q][key] K[key][d], 16x16x32 MFMAs issued as
-    // (K^T fragment, dS fragment): the lane ends up with 4 consecutive d of one query.  Both
-    // fragments (8 consecutive keys per lane) come from transposing reads of [key][.] images.
-    // The key rows a lane reads are a permutation of the natural 8 fg + 4 j + fq (bits 2 and 3
-    // swapped: 16 (fg >> 1) + 8 j + 4 (fg & 1) + fq), the same for both operands, so the sum
-    // over keys is unchanged: each 32-lane half of a transposing read then covers 8
-    // consecutive rows, whose swizzled chunks of K (swz) and of dS^T (dsw) fill all 64 banks
-    // (with the natural order rows r and r + 8 of K shared banks: a 2-way conflict on every
-    // K^T read).
-    f32x4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int kr0 = 32 * ks + 16 * (fg >> 1) + 4 * (fg & 1) + fq, kr1 = kr0 + 8;
-      const int qc = (dq_q0 >> 2) + fp;        // 8-byte chunk of queries dq_q0 + 4 fp .. + 3
-      const bf16x8_t sf = cat_tr(lds_tr(dSt + kr0 * 64 + ((qc ^ dsw(kr0)) << 3)),
-                                 lds_tr(dSt + kr1 * 64 + ((qc ^ dsw(kr1)) << 3)));
-      const bf16x8_t kf0 = cat_tr(lds_tr(Ks + swz_e(kr0, dq_d0 + 4 * fp)), lds_tr(Ks + swz_e(kr1, dq_d0 + 4 * fp)));
-      const bf16x8_t kf1 = cat_tr(lds_tr(Ks + swz_e(kr0, dq_d0 + 16 + 4 * fp)),
-                                  lds_tr(Ks + swz_e(kr1, dq_d0 + 16 + 4 * fp)));
-      dq0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, sf, dq0, 0, 0, 0);
-      dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, sf, dq1, 0, 0, 0);
-    }
-    // dq0[rr] = dQ[q = dq_q0 + (lane & 15)][d = dq_d0 + 4 (lane >> 4) + rr], dq1 the same +16
-    const int q = qb + dq_q0 + (lane & 15);
-    if (single_block && dq16 && qb + 32 <= a.Sq) {
-      const u16x4 o0 = {f2bf(dq0[0] * a.scale), f2bf(dq0[1] * a.scale), f2bf(dq0[2] * a.scale), f2bf(dq0[3] * a.scale)};
-      const u16x4 o1 = {f2bf(dq1[0] * a.scale), f2bf(dq1[1] * a.scale), f2bf(dq1[2] * a.scale), f2bf(dq1[3] * a.scale)};
-      // permlane16 swap of the two d blocks: lane group g gets 8 consecutive d
-      const uint2 xv = __builtin_bit_cast(uint2, o0), yv = __builtin_bit_cast(uint2, o1);
-      const auto s0 = __builtin_amdgcn_permlane16_swap(xv.x, yv.x, false, false);
-      const auto s1 = __builtin_amdgcn_permlane16_swap(xv.y, yv.y, false, false);
-      const uint4 v = {s0[0], s1[0], s0[1], s1[1]};
-      const int d = dq_d0 + 16 * (fg & 1) + 8 * (fg >> 1);
-      *reinterpret_cast<uint4*>(dqbase + q * (int)a.dq_ss + d) = v;
-    } else if (!single_block) {
-      // Sk > 128: the wave's [16 q][32 d] fp32 share goes through LDS so that each atomic
-      // wave-instruction adds two contiguous 128-byte row segments (the memory-side atomic
-      // unit's full-rate shape) instead of 16 rows x 4 scattered dwords (~10x slower: the
-      // backward took 883 us at B 32, S 512 before, 326 after).  Scratch: this wave's own key
-      // rows of the OTHER dS^T buffer (tile qt - 1's, read by every wave's dQ before this
-      // tile's barrier; rewritten only by this wave, at tile qt + 1); 128-byte rows, 16-byte
-      // chunks XOR (q & 7).  Every lane takes part; rows past Sq only skip their atomics.
-      char* xw = dSs + (buf ^ 1) * 8192 + w * 2048;
-      const int xq = lane & 15;
-      *reinterpret_cast<f32x4*>(xw + xq * 128 + ((fg ^ (xq & 7)) << 4)) = dq0;
-      *reinterpret_cast<f32x4*>(xw + xq * 128 + (((4 + fg) ^ (xq & 7)) << 4)) = dq1;
-      __builtin_amdgcn_wave_barrier();
-      const int xd = lane & 31;
-      float* accp = a.dq_acc + ((long)bh * a.Sq + qb + dq_q0) * 64 + dq_d0 + xd;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int qr = 2 * i + (lane >> 5);
-        const float val = *reinterpret_cast<const float*>(xw + qr * 128 + (((xd >> 2) ^ (qr & 7)) << 4) + ((xd & 3) << 2)) * a.scale;
-        if (qb + dq_q0 + qr < a.Sq) atomicAdd(accp + qr * 64, val);
-      }
-      __builtin_amdgcn_wave_barrier();
-    } else if (q < a.Sq) {
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const int d = dq_d0 + 16 * t2 + 4 * fg + rr;
-          dqbase[q * (int)a.dq_ss + d] = f2bf((t2 ? dq1[rr] : dq0[rr]) * a.scale);
-        }
-    }
-  }
-#undef BWD_PREFETCH
-#undef BWD_STAGE
-#undef BWD_GLDS
-  {
-    const long kl = kvalid ? key_l : 0;
-    store_row64(a.dk + b * a.dk_sb + h * a.dk_sh + kl * a.dk_ss, dK0, dK1, a.scale, hh, kvalid);
-    store_row64(a.dv + b * a.dv_sb + h * a.dv_sh + kl * a.dv_ss, dV0, dV1, 1.f, hh, kvalid);
-  }
+  drel[h * d_sh + i * d_si] = acc;
 }
 
 // dq (bf16, strided) = dq_acc (fp32 [B*H, Sq, 64])
@@ -1327,6 +1035,43 @@ extern "C" int ct_attn_fwd_relbias(const void* q, const long* qs, const void* k,
   return 0;
 }
 
+// Training forward with the relative-position bias: ct_attn_fwd_relbias plus the dropout stream
+// of ct_attn_fwd (drop_params; p > 0 needs an even Sk); lse is always written (the backward
+// reads it).  attn_fwd_d64_kernel<DROP, CAUSAL, REL = true>, two workgroups per CU.
+extern "C" int ct_attn_fwd_relbias_train(const void* q, const long* qs, const void* k, const long* ks,
+                                         const void* v, const long* vs, void* o, const long* os,
+                                         const float* kbias, long kb_sb, const float* relb, long relb_sh,
+                                         int relb_len, int rel_base, float* lse, int B, int H, int Sq, int Sk,
+                                         float scale, float p_drop, uint64_t seed, uint64_t offset, int causal,
+                                         hipStream_t stream) {
+  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || relb_len <= 0 || !lse || !relb) return -1;
+  if (p_drop > 0.f && (Sk % 2)) return -2;
+  if (relb_len > kRelBiasMax) return -4;
+  if (!fits32(Sq, qs[1]) || !fits32(Sk, ks[1]) || !fits32(Sk, vs[1]) || !fits32(Sq, os[1])) return -5;
+  if (((uintptr_t)o & 15) || os[0] % 8 || os[1] % 8 || os[2] % 8) return -7;   // 16-byte output stores
+  AttnFwdArgs a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
+  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
+  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
+  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
+  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
+  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse;
+  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  drop_params(p_drop, seed, offset, &a.thr16, &a.inv_keep, &a.hash_base);
+  a.causal = causal;
+  a.relb = relb; a.relb_sh = relb_sh; a.relb_len = relb_len; a.rel_base = rel_base;
+  dim3 grid((Sq + 127) / 128, B * H);
+  if (p_drop > 0.f) {
+    if (causal) attn_fwd_d64_kernel<true, true, true><<<grid, 256, 0, stream>>>(a);
+    else attn_fwd_d64_kernel<true, false, true><<<grid, 256, 0, stream>>>(a);
+  } else {
+    if (causal) attn_fwd_d64_kernel<false, true, true><<<grid, 256, 0, stream>>>(a);
+    else attn_fwd_d64_kernel<false, false, true><<<grid, 256, 0, stream>>>(a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -8;
+}
+
 // Head-dim-128 inference forward (attn_fwd_d128_kernel): the arguments of ct_attn_fwd without
 // dropout plus those of ct_attn_fwd_relbias; relb == nullptr selects the kernel without the
 // relative bias.  Rows are 128 elements, so the 32-bit offset check keeps 128 of slack.
@@ -1400,6 +1145,7 @@ extern "C" int ct_attn_bwd(const void* q, const long* qs, const void* k, const l
   a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
   drop_params(p_drop, seed, offset, &a.thr16, &a.inv_keep, &a.hash_base);
   a.causal = causal;
+  a.relb = nullptr; a.relb_sh = 0; a.relb_len = 0; a.rel_base = 0; a.drel_ws = nullptr;
   const int nkb = (Sk + 127) / 128;
   if (nkb > 1 && !dq_acc) return -3;
   if (nkb > 1) hipMemsetAsync(dq_acc, 0, sizeof(float) * rows * 64, stream);
@@ -1425,6 +1171,82 @@ extern "C" int ct_attn_bwd(const void* q, const long* qs, const void* k, const l
   if (nkb > 1)
     attn_dq_convert_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
         dq_acc, (bf16_t*)dq, dqs[0], dqs[1], dqs[2], B, H, Sq);
+  return 0;
+}
+
+// Relative-bias backward.  W = 32 ceil(Sq / 32) + 127 offsets per workgroup window (see
+// attn_bwd_d64_kernel); the kernel keeps two windows (8 W bytes) of dynamic LDS next to its
+// 66,048 static bytes, and two workgroups per CU (what __launch_bounds__(256, 2) and the
+// register budget are for) leave 160 KiB / 2 - 66,048 = 15,872 bytes: W <= 1984, Sq <= 1856.
+constexpr int kBwdRelMaxWindow = (160 * 1024 / 2 - 66048) / 8;
+extern "C" int ct_attn_bwd_relbias_window(int Sq) { return 32 * ((Sq + 31) / 32) + 127; }
+extern "C" int ct_attn_bwd_relbias_max_window() { return kBwdRelMaxWindow; }
+
+// ct_attn_bwd plus the relative-bias vector of the forward and its gradient: d_rel [H, relb_len]
+// fp32 (strides d_sh, d_si), every entry written.  drel_ws: float[B * nkb * H * W] workspace
+// (nkb = ceil(Sk / 128), W = ct_attn_bwd_relbias_window(Sq)), no need to clear it.  Dispatch:
+// Sk > 128 -> attn_bwd_d64_rel_kernel<DROP, CAUSAL, MULTI = true>, otherwise <.., MULTI = false>,
+// the register-staged single-block form for every Sq (REL has no LDS-DMA form), then
+// attn_drel_reduce_kernel.  rc -9: the windows would not leave room for two workgroups per CU.
+extern "C" int ct_attn_bwd_relbias(const void* q, const long* qs, const void* k, const long* ks,
+                                   const void* v, const long* vs, const void* o, const long* os,
+                                   const void* dO, const long* dos, void* dq, const long* dqs, void* dk,
+                                   const long* dks, void* dv, const long* dvs, const float* kbias,
+                                   long kb_sb, const float* relb, long relb_sh, int relb_len, int rel_base,
+                                   float* d_rel, long d_sh, long d_si, const float* lse, float* dq_acc,
+                                   float* drel_ws, int B, int H, int Sq, int Sk, float scale, float p_drop,
+                                   uint64_t seed, uint64_t offset, int causal, hipStream_t stream) {
+  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || relb_len <= 0 || !relb || !d_rel || !drel_ws) return -1;
+  if (p_drop > 0.f && (Sk % 2)) return -2;
+  if (relb_len > kRelBiasMax) return -4;
+  if (rel_base < Sq - 1 || (long)rel_base + Sk > relb_len) return -10;   // relb must cover every offset
+  if (!fits32(Sq, qs[1]) || !fits32(Sk, ks[1]) || !fits32(Sk, vs[1]) || !fits32(Sq, os[1]) ||
+      !fits32(Sq, dos[1]) || !fits32(Sq, dqs[1])) return -5;
+  if (((uintptr_t)dk & 15) || ((uintptr_t)dv & 15) || dks[0] % 8 || dks[1] % 8 || dks[2] % 8 || dvs[0] % 8 ||
+      dvs[1] % 8 || dvs[2] % 8)
+    return -7;
+  const int W = ct_attn_bwd_relbias_window(Sq);
+  if (W > kBwdRelMaxWindow) return -9;
+  const long rows = (long)B * H * Sq;
+  AttnBwdArgs a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.dO = (const bf16_t*)dO;
+  a.o = (const bf16_t*)o; a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
+  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.dq_acc = dq_acc;
+  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
+  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
+  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
+  a.do_sb = dos[0]; a.do_ss = dos[1]; a.do_sh = dos[2];
+  a.dq_sb = dqs[0]; a.dq_ss = dqs[1]; a.dq_sh = dqs[2];
+  a.dk_sb = dks[0]; a.dk_ss = dks[1]; a.dk_sh = dks[2];
+  a.dv_sb = dvs[0]; a.dv_ss = dvs[1]; a.dv_sh = dvs[2];
+  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse; a.delta = nullptr;
+  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
+  a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
+  drop_params(p_drop, seed, offset, &a.thr16, &a.inv_keep, &a.hash_base);
+  a.causal = causal;
+  a.relb = relb; a.relb_sh = relb_sh; a.relb_len = relb_len; a.rel_base = rel_base; a.drel_ws = drel_ws;
+  const int nkb = (Sk + 127) / 128;
+  if (nkb > 1 && !dq_acc) return -3;
+  if (nkb > 1) hipMemsetAsync(dq_acc, 0, sizeof(float) * rows * 64, stream);
+  dim3 grid(nkb, B * H);
+  const size_t dyn = (size_t)W * 2 * sizeof(float);
+#define CT_ATTN_BWD_REL(M)                                                                 \
+  if (p_drop > 0.f) {                                                                      \
+    if (causal) attn_bwd_d64_rel_kernel<true, true, M><<<grid, 256, dyn, stream>>>(a);     \
+    else attn_bwd_d64_rel_kernel<true, false, M><<<grid, 256, dyn, stream>>>(a);           \
+  } else {                                                                                 \
+    if (causal) attn_bwd_d64_rel_kernel<false, true, M><<<grid, 256, dyn, stream>>>(a);    \
+    else attn_bwd_d64_rel_kernel<false, false, M><<<grid, 256, dyn, stream>>>(a);          \
+  }
+  if (nkb > 1) { CT_ATTN_BWD_REL(true) } else { CT_ATTN_BWD_REL(false) }
+#undef CT_ATTN_BWD_REL
+  if (hipGetLastError() != hipSuccess) return -8;
+  if (nkb > 1)
+    attn_dq_convert_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
+        dq_acc, (bf16_t*)dq, dqs[0], dqs[1], dqs[2], B, H, Sq);
+  // window of key block 0 starts at offset 1 - 32 nq + rel_base = rel_base + 128 - W
+  attn_drel_reduce_kernel<<<(H * relb_len + 255) / 256, 256, 0, stream>>>(
+      drel_ws, d_rel, d_sh, d_si, B, nkb, H, W, relb_len, rel_base + 128 - W);
   return 0;
 }
 

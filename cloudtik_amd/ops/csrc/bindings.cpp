@@ -79,6 +79,16 @@ int ct_attn_bwd(const void*, const long*, const void*, const long*, const void*,
                 const void*, const long*, const void*, const long*, void*, const long*, void*,
                 const long*, void*, const long*, const float*, long, const float*, float*, float*,
                 int, int, int, int, float, float, uint64_t, uint64_t, int, hipStream_t);
+int ct_attn_fwd_relbias_train(const void*, const long*, const void*, const long*, const void*, const long*, void*,
+                              const long*, const float*, long, const float*, long, int, int, float*, int, int, int,
+                              int, float, float, uint64_t, uint64_t, int, hipStream_t);
+int ct_attn_bwd_relbias_window(int);
+int ct_attn_bwd_relbias_max_window();
+int ct_attn_bwd_relbias(const void*, const long*, const void*, const long*, const void*, const long*,
+                        const void*, const long*, const void*, const long*, void*, const long*, void*,
+                        const long*, void*, const long*, const float*, long, const float*, long, int, int,
+                        float*, long, long, const float*, float*, float*, int, int, int, int, float, float,
+                        uint64_t, uint64_t, int, hipStream_t);
 }
 
 #define CHECK_CUDA(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")
@@ -528,6 +538,84 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
                        B, H, Sq, Sk, (float)scale, (float)p, (uint64_t)seed, (uint64_t)offset,
                        causal ? 1 : 0, cur_stream());
   TORCH_CHECK(rc == 0, "attn_bwd failed rc=", rc);
+}
+
+// ---- relative-bias attention for training (T5, head dim 64): forward with dropout + lse, and a
+// backward that also returns the gradient of the bias vector
+static const float* relb_checked(const at::Tensor& relb, int H, int Sq, int Sk, int64_t rel_base, long* L) {
+  CHECK_F32(relb); CHECK_CUDA(relb);
+  TORCH_CHECK(relb.dim() == 2 && relb.size(0) == H && (relb.stride(1) == 1 || relb.size(1) == 1),
+              "relb must be [H, L] fp32");
+  *L = relb.size(1);
+  TORCH_CHECK(rel_base >= Sq - 1 && rel_base + Sk <= *L, "relb does not cover every (key - query) offset");
+  return relb.data_ptr<float>();
+}
+static const float* key_bias_checked(const c10::optional<at::Tensor>& key_bias, int B, int Sk, long* kb_sb) {
+  *kb_sb = 0;
+  if (!(key_bias.has_value() && key_bias->defined())) return nullptr;
+  CHECK_F32(*key_bias); CHECK_CUDA(*key_bias);
+  TORCH_CHECK(key_bias->dim() == 2 && key_bias->size(0) == B && key_bias->size(1) == Sk && key_bias->stride(1) == 1);
+  *kb_sb = key_bias->stride(0);
+  return key_bias->data_ptr<float>();
+}
+
+at::Tensor attn_fwd_relbias_train(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                                  c10::optional<at::Tensor> key_bias, at::Tensor relb, int64_t rel_base,
+                                  double scale, double p, int64_t seed, int64_t offset, bool causal) {
+  long qs[3], ks[3], vs[3], os[3];
+  bshd_strides_bwd(q, qs, "q"); bshd_strides_bwd(k, ks, "k"); bshd_strides_bwd(v, vs, "v"); bshd_strides_bwd(o, os, "o");
+  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
+  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
+  long L, kb_sb;
+  const float* rp = relb_checked(relb, H, Sq, Sk, rel_base, &L);
+  const float* kb = key_bias_checked(key_bias, B, Sk, &kb_sb);
+  auto lse = at::empty({(long)B * H, Sq}, q.options().dtype(at::kFloat));
+  int rc = ct_attn_fwd_relbias_train(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb,
+                                     kb_sb, rp, relb.stride(0), (int)std::min<long>(L, 1 << 20), (int)rel_base,
+                                     lse.data_ptr<float>(), B, H, Sq, Sk, (float)scale, (float)p, (uint64_t)seed,
+                                     (uint64_t)offset, causal ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, "attn_fwd_relbias_train failed rc=", rc);
+  return lse;
+}
+
+// d_rel: fp32 [H, L] in any strides (the gradient in the layout of the caller's bias view); every
+// entry is written.  rc=-9: Sq too long for the kernel's LDS windows (callers fall back).
+void attn_bwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dO, at::Tensor dq,
+                      at::Tensor dk, at::Tensor dv, at::Tensor d_rel, c10::optional<at::Tensor> key_bias,
+                      at::Tensor relb, int64_t rel_base, at::Tensor lse, double scale, double p, int64_t seed,
+                      int64_t offset, bool causal) {
+  long qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
+  bshd_strides_bwd(q, qs, "q"); bshd_strides_bwd(k, ks, "k"); bshd_strides_bwd(v, vs, "v"); bshd_strides_bwd(o, os, "o");
+  bshd_strides_bwd(dO, dos, "dO"); bshd_strides_bwd(dq, dqs, "dq"); bshd_strides_bwd(dk, dks, "dk"); bshd_strides_bwd(dv, dvs, "dv");
+  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
+  TORCH_CHECK(dO.sizes() == o.sizes() && dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes());
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
+  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
+  CHECK_F32(lse); CHECK_CUDA(lse);
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == (long)B * H * Sq, "lse must be contiguous fp32 [B*H, Sq]");
+  long L, kb_sb;
+  const float* rp = relb_checked(relb, H, Sq, Sk, rel_base, &L);
+  const float* kb = key_bias_checked(key_bias, B, Sk, &kb_sb);
+  CHECK_F32(d_rel); CHECK_CUDA(d_rel);
+  TORCH_CHECK(d_rel.dim() == 2 && d_rel.size(0) == H && d_rel.size(1) == L, "d_rel must be fp32 [H, L] like relb");
+  TORCH_CHECK(L <= 1 || H <= 1 || (d_rel.stride(0) != 0 && d_rel.stride(1) != 0), "d_rel must not be an expanded view");
+  auto fo = q.options().dtype(at::kFloat);
+  const int nkb = (Sk + 127) / 128;
+  const long W = ct_attn_bwd_relbias_window(Sq);
+  at::Tensor dq_acc, ws;
+  // the C entry refuses L > 4096 and windows past the LDS budget before it touches a workspace
+  const bool sized = L <= 4096 && W <= ct_attn_bwd_relbias_max_window();
+  if (Sk > 128 && sized) dq_acc = at::empty({(long)B * H * Sq * 64}, fo);
+  ws = at::empty({sized ? (long)B * nkb * H * W : 1L}, fo);
+  int rc = ct_attn_bwd_relbias(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, dO.data_ptr(),
+                               dos, dq.data_ptr(), dqs, dk.data_ptr(), dks, dv.data_ptr(), dvs, kb, kb_sb, rp,
+                               relb.stride(0), (int)std::min<long>(L, 1 << 20), (int)rel_base,
+                               d_rel.data_ptr<float>(), d_rel.stride(0), d_rel.stride(1), lse.data_ptr<float>(),
+                               dq_acc.defined() ? dq_acc.data_ptr<float>() : nullptr, ws.data_ptr<float>(), B, H, Sq,
+                               Sk, (float)scale, (float)p, (uint64_t)seed, (uint64_t)offset, causal ? 1 : 0,
+                               cur_stream());
+  TORCH_CHECK(rc == 0, "attn_bwd_relbias failed rc=", rc);
 }
 
 // ---------------------------------------------------------------- batchnorm (NHWC)
@@ -980,4 +1068,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_relbias", &attn_fwd_relbias);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_fwd_relbias_train", &attn_fwd_relbias_train);
+  m.def("attn_bwd_relbias", &attn_bwd_relbias);
+  m.def("attn_bwd_relbias_window", [](int64_t Sq) { return (int64_t)ct_attn_bwd_relbias_window((int)Sq); });
+  m.def("attn_bwd_relbias_max_window", []() { return (int64_t)ct_attn_bwd_relbias_max_window(); });
 }
