@@ -38,7 +38,7 @@ int ct_lamb(const void*, int, float*, float*, float*, void*, int, const int*, co
 int ct_adam(const void*, int, float*, float*, float*, void*, int, const int*, const long*,
             const int*, int, const float*, const float*, float, float, float, int, hipStream_t);
 int ct_sgd(const void*, int, float*, float*, void*, int, const int*, const long*, const int*, int,
-           const float*, const float*, float, float, int, int, hipStream_t);
+           const float*, const float*, float, float, int, hipStream_t);
 int ct_sumsq(const void*, int, long, float*, float*, hipStream_t);
 int ct_clip_coef(const float*, float*, float, float, hipStream_t);
 int ct_xent_fwd(const void*, void*, int, int, const int64_t*, float*, float*, const float*, int, int,
@@ -348,6 +348,7 @@ void lamb_step(at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor w, c10::opti
   TORCH_CHECK(g.numel() >= w.numel() && m.numel() == w.numel() && v.numel() == w.numel());
   const int nseg = seg_len.numel(), T = tensor_wd.numel();
   TORCH_CHECK(seg_part.numel() >= 2 * nseg && tensor_part.numel() >= 2 * T && tensor_first_seg.numel() == T + 1);
+  TORCH_CHECK(dyn.numel() >= 4, "lamb_step: dyn holds lr, grad scale and two bias corrections");
   int pdt = 0;
   if (w_model.has_value() && w_model->defined()) { CHECK_IN(*w_model); pdt = dt_code(*w_model); TORCH_CHECK(w_model->numel() >= w.numel()); }
   ct_lamb(g.data_ptr(), dt_code(g), m.data_ptr<float>(), v.data_ptr<float>(), w.data_ptr<float>(),
@@ -364,8 +365,12 @@ void adam_step(at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor w, c10::opti
   for (auto* t : {&g, &m, &v, &w, &seg_tensor, &seg_start, &seg_len, &tensor_wd, &dyn}) CHECK_IN(*t);
   CHECK_F32(m); CHECK_F32(v); CHECK_F32(w);
   TORCH_CHECK(g.numel() >= w.numel() && m.numel() == w.numel() && v.numel() == w.numel());
+  TORCH_CHECK(dyn.numel() >= 4, "adam_step: dyn holds lr, grad scale and two bias corrections");
   int pdt = 0;
-  if (w_model.has_value() && w_model->defined()) { CHECK_IN(*w_model); pdt = dt_code(*w_model); }
+  if (w_model.has_value() && w_model->defined()) {
+    CHECK_IN(*w_model); pdt = dt_code(*w_model);
+    TORCH_CHECK(w_model->numel() >= w.numel(), "adam_step: w_model is shorter than w");
+  }
   ct_adam(g.data_ptr(), dt_code(g), m.data_ptr<float>(), v.data_ptr<float>(), w.data_ptr<float>(),
           optr_mut(w_model), pdt, seg_tensor.data_ptr<int>(), seg_start.data_ptr<int64_t>(),
           seg_len.data_ptr<int>(), seg_len.numel(), tensor_wd.data_ptr<float>(), dyn.data_ptr<float>(),
@@ -374,17 +379,25 @@ void adam_step(at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor w, c10::opti
 
 void sgd_step(at::Tensor g, c10::optional<at::Tensor> buf, at::Tensor w, c10::optional<at::Tensor> w_model,
               at::Tensor seg_tensor, at::Tensor seg_start, at::Tensor seg_len, at::Tensor tensor_wd,
-              at::Tensor dyn, double momentum, double dampening, bool nesterov, bool first) {
+              at::Tensor dyn, double momentum, double dampening, bool nesterov) {
   for (auto* t : {&g, &w, &seg_tensor, &seg_start, &seg_len, &tensor_wd, &dyn}) CHECK_IN(*t);
   CHECK_F32(w);
   TORCH_CHECK(g.numel() >= w.numel());
-  if (momentum != 0.0) TORCH_CHECK(buf.has_value() && buf->defined() && buf->numel() == w.numel(), "momentum buffer");
+  TORCH_CHECK(dyn.numel() >= 3, "sgd_step: dyn holds lr, grad scale and the first-step flag");
+  if (momentum != 0.0) {
+    TORCH_CHECK(buf.has_value() && buf->defined() && buf->numel() == w.numel(), "momentum buffer");
+    CHECK_IN(*buf); CHECK_F32(*buf);
+  }
   int pdt = 0;
-  if (w_model.has_value() && w_model->defined()) { CHECK_IN(*w_model); pdt = dt_code(*w_model); }
-  ct_sgd(g.data_ptr(), dt_code(g), (float*)optr_mut(buf), w.data_ptr<float>(), optr_mut(w_model), pdt,
-         seg_tensor.data_ptr<int>(), seg_start.data_ptr<int64_t>(), seg_len.data_ptr<int>(), seg_len.numel(),
-         tensor_wd.data_ptr<float>(), dyn.data_ptr<float>(), (float)momentum, (float)dampening,
-         nesterov ? 1 : 0, first ? 1 : 0, cur_stream());
+  if (w_model.has_value() && w_model->defined()) {
+    CHECK_IN(*w_model); pdt = dt_code(*w_model);
+    TORCH_CHECK(w_model->numel() >= w.numel(), "sgd_step: w_model is shorter than w");
+  }
+  // momentum == 0: the kernel never touches buf
+  ct_sgd(g.data_ptr(), dt_code(g), momentum != 0.0 ? (float*)optr_mut(buf) : nullptr, w.data_ptr<float>(),
+         optr_mut(w_model), pdt, seg_tensor.data_ptr<int>(), seg_start.data_ptr<int64_t>(),
+         seg_len.data_ptr<int>(), seg_len.numel(), tensor_wd.data_ptr<float>(), dyn.data_ptr<float>(),
+         (float)momentum, (float)dampening, nesterov ? 1 : 0, cur_stream());
 }
 
 void sumsq_into(at::Tensor x, at::Tensor out) {
@@ -395,6 +408,8 @@ void sumsq_into(at::Tensor x, at::Tensor out) {
 }
 
 void clip_coef(at::Tensor sumsq, at::Tensor dyn, double base_scale, double max_norm) {
+  CHECK_IN(sumsq); CHECK_IN(dyn); CHECK_F32(sumsq); CHECK_F32(dyn);
+  TORCH_CHECK(sumsq.numel() >= 1 && dyn.numel() >= 4, "clip_coef: sumsq [1], dyn [>= 4]");
   ct_clip_coef(sumsq.data_ptr<float>(), dyn.data_ptr<float>(), (float)base_scale, (float)max_norm, cur_stream());
 }
 

@@ -27,7 +27,7 @@
 namespace ct {
 
 // dyn[0] = lr, dyn[1] = grad scale (e.g. 1/world or clip coef), dyn[2] = 1/(1-b1^t),
-// dyn[3] = 1/(1-b2^t)
+// dyn[3] = 1/(1-b2^t); SGD has no bias corrections: its dyn[2] is the first-step flag (1 or 0)
 struct OptSegs {
   const int* seg_tensor;    // [nseg]
   const long* seg_start;    // [nseg] element offset in the flat space
@@ -296,17 +296,20 @@ __global__ __launch_bounds__(256) void adam_kernel(
   }
 }
 
-// SGD with momentum (PyTorch semantics: buf = mom*buf + (1-damp)*g; nesterov g + mom*buf)
+// SGD with momentum (PyTorch semantics: buf = mom*buf + (1-damp)*g; nesterov g + mom*buf).
+// The first step (buf = g) is flagged by dyn[2] != 0, not by a kernel argument: a captured
+// launch replays its arguments, so a host flag taken at step 1 would hold for every replay.
 template <typename GT, typename PT>
 __global__ __launch_bounds__(256) void sgd_kernel(
     const GT* __restrict__ g, float* __restrict__ buf, float* __restrict__ w,
     PT* __restrict__ w_model, OptSegs segs, const float* __restrict__ tensor_wd,
-    const float* __restrict__ dyn, float momentum, float dampening, int nesterov, int first) {
+    const float* __restrict__ dyn, float momentum, float dampening, int nesterov) {
   const int s = blockIdx.x;
   const long start = segs.seg_start[s];
   const int len = segs.seg_len[s];
   const float wd = tensor_wd[segs.seg_tensor[s]];
   const float lr = dyn[0], gs = dyn[1];
+  const bool first = dyn[2] != 0.f;
   for (int i = threadIdx.x * 4; i < len; i += blockDim.x * 4) {
     const long k = start + i;
     const f32x4 gv = load4<GT>(g, k);
@@ -417,9 +420,9 @@ extern "C" int ct_adam(const void* g, int gdt, float* m, float* v, float* w, voi
 extern "C" int ct_sgd(const void* g, int gdt, float* buf, float* w, void* w_model, int pdt,
                       const int* seg_tensor, const long* seg_start, const int* seg_len, int nseg,
                       const float* tensor_wd, const float* dyn, float momentum, float dampening,
-                      int nesterov, int first, hipStream_t stream) {
+                      int nesterov, hipStream_t stream) {
   OptSegs segs{seg_tensor, seg_start, seg_len};
-#define CT_SGD(GT, PT) sgd_kernel<GT, PT><<<nseg, 256, 0, stream>>>((const GT*)g, buf, w, (PT*)w_model, segs, tensor_wd, dyn, momentum, dampening, nesterov, first)
+#define CT_SGD(GT, PT) sgd_kernel<GT, PT><<<nseg, 256, 0, stream>>>((const GT*)g, buf, w, (PT*)w_model, segs, tensor_wd, dyn, momentum, dampening, nesterov)
   if (gdt == 1 && pdt == 1) CT_SGD(bf16_t, bf16_t);
   else if (gdt == 1) CT_SGD(bf16_t, float);
   else if (pdt == 1) CT_SGD(float, bf16_t);

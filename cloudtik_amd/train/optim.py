@@ -276,6 +276,12 @@ class FlatParamSpace:
             self.master.copy_(self.shard_model.float())
 
 
+def _one_minus(beta: float) -> float:
+    """1 - beta as the kernels form it: from beta rounded to an fp32 argument (1.f - 0.999f is
+    1.3e-5 from 0.001), so the PyTorch paths run the same recurrence as csrc/optim.hip."""
+    return 1.0 - float(torch.tensor(beta, dtype=torch.float32))
+
+
 def _is_native(t: torch.Tensor) -> bool:
     if not t.is_cuda:
         return False
@@ -373,7 +379,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         """Before replaying a captured training step (the capture itself ran no kernels): count
         the step and put its scalars (lr, grad scale, bias corrections) where the graph's copy
         node reads them.  The slot is only rewritten -- after the previous replay finished with
-        it -- when a value changes (never for a constant-lr SGD)."""
+        it -- when a value changes (for a constant-lr SGD: once, when its first-step flag drops)."""
         if getattr(self, "_graph_host", None) is None:
             return
         if self._graph_replays > 0:
@@ -526,8 +532,8 @@ class FusedLAMB(_FlatOptimizer):
             coef = torch.clamp(self.max_grad_norm / (nrm.sqrt() + 1e-6), max=1.0)
             gf = gf * coef
         m, v, w = self.exp_avg, self.exp_avg_sq, sp.shard_params
-        m.mul_(b1).add_(gf, alpha=1 - b1)
-        v.mul_(b2).addcmul_(gf, gf, value=1 - b2)
+        m.mul_(b1).add_(gf, alpha=_one_minus(b1))
+        v.mul_(b2).addcmul_(gf, gf, value=_one_minus(b2))
         wd = self._per_elem(self._wd)
         u = (m * bc1) / ((v * bc2).sqrt() + self.eps) + wd * w
         T = len(sp.params)
@@ -601,8 +607,8 @@ class FusedAdam(_FlatOptimizer):
             gf = g.float() * gs
             if not self.adamw:
                 gf = gf + wd * w
-            self.exp_avg.mul_(b1).add_(gf, alpha=1 - b1)
-            self.exp_avg_sq.mul_(b2).addcmul_(gf, gf, value=1 - b2)
+            self.exp_avg.mul_(b1).add_(gf, alpha=_one_minus(b1))
+            self.exp_avg_sq.mul_(b2).addcmul_(gf, gf, value=_one_minus(b2))
             upd = (self.exp_avg / (1 - b1 ** t)) / ((self.exp_avg_sq / (1 - b2 ** t)).sqrt() + self.eps)
             if self.adamw:
                 upd = upd + wd * w
@@ -626,6 +632,13 @@ class FusedSGD(_FlatOptimizer):
     def _flat_state(self):
         return {"momentum_buffer": self.momentum_buffer} if self.momentum_buffer is not None else {}
 
+    def _dyn_values(self, b1, b2):
+        # SGD has no bias corrections: slot 2 carries the first-step flag (buf = g).  A host
+        # argument would be frozen into a captured launch; the slot is refreshed per replay.
+        vals = super()._dyn_values(None, None)
+        vals[2] = 1.0 if self.step_count == 1 else 0.0
+        return vals
+
     @torch.no_grad()
     def step(self, closure=None):
         _sync_grads()
@@ -641,7 +654,7 @@ class FusedSGD(_FlatOptimizer):
             wm = sp.shard_model if sp.master is not None else None
             ops.require_native().sgd_step(g, self.momentum_buffer, sp.shard_params, wm, sp.seg_tensor,
                                           sp.seg_start, sp.seg_len, self._wd, self.dyn,
-                                          self.momentum, self.dampening, self.nesterov, first)
+                                          self.momentum, self.dampening, self.nesterov)
         else:
             w = sp.shard_params
             wd = LAMBHelper.per_elem(self, self._wd)
@@ -651,7 +664,7 @@ class FusedSGD(_FlatOptimizer):
                 if first:
                     b.copy_(gf)
                 else:
-                    b.mul_(self.momentum).add_(gf, alpha=1 - self.dampening)
+                    b.mul_(self.momentum).add_(gf, alpha=_one_minus(self.dampening))
                 gf = gf + self.momentum * b if self.nesterov else b
             w.sub_(self._lr() * gf)
             if sp.master is not None:

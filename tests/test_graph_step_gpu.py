@@ -69,3 +69,46 @@ def test_graph_slot_carries_per_step_bias_corrections():
     torch.cuda.synchronize()
     assert opt.step_count == opt_ref.step_count == 8
     torch.testing.assert_close(w.detach(), w_ref.detach(), rtol=1e-5, atol=1e-6)
+
+
+def _graphed_sgd_follows_fp64(dampening, warmup):
+    """FusedSGD(momentum=0.9) on one 4096-element parameter for 4 steps under GraphedStep, a new
+    gradient copied into the static buffer before every call; after each step the weights are
+    compared with an fp64 SGD (PyTorch rule: buf = g on the first step, then
+    buf = 0.9 buf + (1 - dampening) g; w -= lr buf).  Tolerance: 4 steps of fp32 rounding, one
+    ulp (1.2e-7) of the value each: rtol 1e-6; where the terms cancel the error is an ulp of
+    the terms, which stay below 8 (ulp 4.8e-7) here: atol 1e-6.  A momentum that is not
+    accumulated is off by lr x 0.9 x |buf|, about 5e-2."""
+    from cloudtik_amd.train.graph_step import GraphedStep
+    from cloudtik_amd.train.optim import FlatParamSpace, FusedSGD
+    n, lr, mom, steps = 4096, 0.05, 0.9, 4
+    gen = torch.Generator().manual_seed(11)
+    w0 = torch.randn(n, generator=gen)
+    grads = [torch.randn(n, generator=gen) for _ in range(steps)]
+    w = torch.nn.Parameter(w0.clone().cuda())
+    sp = FlatParamSpace([w], names=["w"])
+    opt = FusedSGD(sp, lr=lr, momentum=mom, dampening=dampening, space=sp)
+    step = GraphedStep(opt.step, optimizers=[opt], warmup=warmup)
+    ref, buf = w0.double(), None
+    for i, g in enumerate(grads):
+        sp.grad[:n].copy_(g.cuda())
+        step()
+        torch.cuda.synchronize()
+        g = g.double()
+        buf = g.clone() if buf is None else mom * buf + (1 - dampening) * g
+        ref = ref - lr * buf
+        torch.testing.assert_close(w.detach().double().cpu(), ref, rtol=1e-6, atol=1e-6,
+                                   msg=lambda m: "step %d: %s" % (i + 1, m))
+        torch.testing.assert_close(opt.momentum_buffer[:n].double().cpu(), buf, rtol=1e-6, atol=1e-6,
+                                   msg=lambda m: "momentum buffer, step %d: %s" % (i + 1, m))
+    assert step.graph is not None and opt.step_count == steps
+
+
+def test_graphed_sgd_captured_at_first_step_accumulates_momentum():
+    """warmup=0 captures at step_count == 1: the first-step rule (buf = g) must hold for the
+    first replay only, so the flag may not be a captured kernel argument."""
+    _graphed_sgd_follows_fp64(dampening=0.0, warmup=0)
+
+
+def test_graphed_sgd_with_dampening_after_warmup():
+    _graphed_sgd_follows_fp64(dampening=0.3, warmup=2)
