@@ -42,6 +42,7 @@
 // global_load_lds into a two-deep ring; the relative-bias stage is dynamic LDS sized to the
 // vector, so two workgroups share a CU.
 #include "common.h"
+#include "attention_api.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -892,6 +893,8 @@ __global__ void attn_dq_convert_kernel(const float* __restrict__ acc, bf16_t* __
 
 using namespace ct;
 
+static_assert(kRelBiasMax == kCtAttnRelBiasMax, "the kernels' LDS stage is the interface's limit");
+
 static uint32_t host_hash_u32(uint32_t x) {
   x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
   return x;
@@ -918,260 +921,23 @@ static int attn_cu_count() {
   return cache[dev];
 }
 
+// an environment knob; every caller keeps the value in a function-local static (read once per process)
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 // Persistent grid of a kernel with `per_cu` resident workgroups per CU over `nitems` work
 // items: every workgroup takes ceil(nitems / slots) items and the grid is the fewest
 // workgroups that need no more rounds than that.  CLOUDTIK_AMD_ATTN_PERSIST=0: one
 // workgroup per item.
 static int attn_persistent_grid(long nitems, int per_cu) {
-  static const int on = [] {
-    const char* e = getenv("CLOUDTIK_AMD_ATTN_PERSIST");
-    return e ? atoi(e) : 1;
-  }();
+  static const int on = env_int("CLOUDTIK_AMD_ATTN_PERSIST", 1);
   if (!on || nitems <= 0) return (int)nitems;
   const long slots = (long)attn_cu_count() * per_cu;
   if (nitems <= slots) return (int)nitems;
   const long rounds = (nitems + slots - 1) / slots;
   return (int)((nitems + rounds - 1) / rounds);
-}
-
-// strides: [batch, seq, head] in elements for each tensor; head_dim must be 64 (contiguous)
-// the kernels index rows inside one (batch, head) slice with 32-bit offsets
-static inline bool fits32(long rows, long row_stride) { return rows * row_stride + 64 < (1L << 31); }
-
-extern "C" int ct_attn_fwd(const void* q, const long* qs, const void* k, const long* ks,
-                           const void* v, const long* vs, void* o, const long* os,
-                           const float* kbias, long kb_sb, float* lse, int B, int H, int Sq,
-                           int Sk, float scale, float p_drop, uint64_t seed, uint64_t offset,
-                           int causal, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return -1;
-  if (p_drop > 0.f && (Sk % 2)) return -2;
-  if (!fits32(Sq, qs[1]) || !fits32(Sk, ks[1]) || !fits32(Sk, vs[1]) || !fits32(Sq, os[1])) return -5;
-  // 16-byte output stores (attn_fwd_d64_kernel's epilogue)
-  if (((uintptr_t)o & 15) || os[0] % 8 || os[1] % 8 || os[2] % 8) return -7;
-  AttnFwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
-  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  drop_params(p_drop, seed, offset, &a.thr16, &a.inv_keep, &a.hash_base);
-  a.causal = causal;
-  a.relb = nullptr; a.relb_sh = 0; a.relb_len = 0; a.rel_base = 0;
-  dim3 grid((Sq + 127) / 128, B * H);
-  const bool drop = p_drop > 0.f;
-  // default: 2 waves/SIMD.  (r3: 3 with dropout, 168 VGPRs, 74-75 vs 77-78 us per BERT-large
-  // layer; since both K/V tiles of an S <= 128 item load up front the 3-wave build spills one
-  // register and the BERT-large step is 0.03-0.06 ms faster at 2 in three interleaved rounds:
-  // 72.63 / 72.60 / 72.36 vs 72.57 / 72.55 / 72.34 ms)
-  static const int wpe_env = [] {
-    const char* e = getenv("CLOUDTIK_AMD_ATTN_FWD_WPE");
-    return e ? atoi(e) : 0;
-  }();
-  static const int gl = [] {
-    const char* e = getenv("CLOUDTIK_AMD_ATTN_FWD_GLDS");
-    return e ? atoi(e) : 1;
-  }();
-  const int wpe = (wpe_env >= 1 && wpe_env <= 4) ? wpe_env : (gl ? 3 : 2);
-  static const int pipe = [] {
-    // opt-in: measured slower than the one-item kernel on BERT-large shapes (B 256, S 128,
-    // p 0.1: 75.5 us persistent / 84.9 us one item per workgroup vs 65.9 us;
-    // profiles/r3/attention_persistent_ab.md)
-    const char* e = getenv("CLOUDTIK_AMD_ATTN_FWD_PIPE");
-    return e ? atoi(e) : 0;
-  }();
-  if (pipe) {
-    const long nitems = (long)((Sq + 127) / 128) * B * H;
-    if (nitems > (1L << 30)) return -6;
-    const int g1 = attn_persistent_grid(nitems, 2);
-    if (drop && causal) attn_fwd_pipe_kernel<true, true><<<g1, 256, 0, stream>>>(a);
-    else if (drop) attn_fwd_pipe_kernel<true, false><<<g1, 256, 0, stream>>>(a);
-    else if (causal) attn_fwd_pipe_kernel<false, true><<<g1, 256, 0, stream>>>(a);
-    else attn_fwd_pipe_kernel<false, false><<<g1, 256, 0, stream>>>(a);
-    return 0;
-  }
-#define CT_ATTN_FWD(W, G)                                                                          \
-  if (drop && causal) attn_fwd_d64_kernel<true, true, false, W, G><<<grid, 256, 0, stream>>>(a);    \
-  else if (drop) attn_fwd_d64_kernel<true, false, false, W, G><<<grid, 256, 0, stream>>>(a);        \
-  else if (causal) attn_fwd_d64_kernel<false, true, false, W, G><<<grid, 256, 0, stream>>>(a);      \
-  else attn_fwd_d64_kernel<false, false, false, W, G><<<grid, 256, 0, stream>>>(a);
-  if (gl) {
-    if (wpe == 4) { CT_ATTN_FWD(4, true) } else if (wpe == 3) { CT_ATTN_FWD(3, true) } else { CT_ATTN_FWD(2, true) }
-  } else {
-    if (wpe == 3) { CT_ATTN_FWD(3, false) } else if (wpe == 1) { CT_ATTN_FWD(1, false) } else { CT_ATTN_FWD(2, false) }
-  }
-#undef CT_ATTN_FWD
-  return 0;
-}
-
-// Forward with a per-head relative-position bias vector relb [H, relb_len] (row stride
-// relb_sh): score(q, k) += relb[h][k - q + rel_base].  Inference path (no dropout).
-extern "C" int ct_attn_fwd_relbias(const void* q, const long* qs, const void* k, const long* ks,
-                                   const void* v, const long* vs, void* o, const long* os,
-                                   const float* kbias, long kb_sb, const float* relb, long relb_sh,
-                                   int relb_len, int rel_base, float* lse, int B, int H, int Sq, int Sk,
-                                   float scale, int causal, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || relb_len <= 0) return -1;
-  if (relb_len > kRelBiasMax) return -4;
-  if (!fits32(Sq, qs[1]) || !fits32(Sk, ks[1]) || !fits32(Sk, vs[1]) || !fits32(Sq, os[1])) return -5;
-  if (((uintptr_t)o & 15) || os[0] % 8 || os[1] % 8 || os[2] % 8) return -7;   // 16-byte output stores
-  AttnFwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
-  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.thr16 = 0; a.inv_keep = 1.f; a.hash_base = 0;
-  a.causal = causal;
-  a.relb = relb; a.relb_sh = relb_sh; a.relb_len = relb_len; a.rel_base = rel_base;
-  dim3 grid((Sq + 127) / 128, B * H);
-  if (causal) attn_fwd_d64_kernel<false, true, true><<<grid, 256, 0, stream>>>(a);
-  else attn_fwd_d64_kernel<false, false, true><<<grid, 256, 0, stream>>>(a);
-  return 0;
-}
-
-// Training forward with the relative-position bias: ct_attn_fwd_relbias plus the dropout stream
-// of ct_attn_fwd (drop_params; p > 0 needs an even Sk); lse is always written (the backward
-// reads it).  attn_fwd_d64_kernel<DROP, CAUSAL, REL = true>, two workgroups per CU.
-extern "C" int ct_attn_fwd_relbias_train(const void* q, const long* qs, const void* k, const long* ks,
-                                         const void* v, const long* vs, void* o, const long* os,
-                                         const float* kbias, long kb_sb, const float* relb, long relb_sh,
-                                         int relb_len, int rel_base, float* lse, int B, int H, int Sq, int Sk,
-                                         float scale, float p_drop, uint64_t seed, uint64_t offset, int causal,
-                                         hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || relb_len <= 0 || !lse || !relb) return -1;
-  if (p_drop > 0.f && (Sk % 2)) return -2;
-  if (relb_len > kRelBiasMax) return -4;
-  if (!fits32(Sq, qs[1]) || !fits32(Sk, ks[1]) || !fits32(Sk, vs[1]) || !fits32(Sq, os[1])) return -5;
-  if (((uintptr_t)o & 15) || os[0] % 8 || os[1] % 8 || os[2] % 8) return -7;   // 16-byte output stores
-  AttnFwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
-  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  drop_params(p_drop, seed, offset, &a.thr16, &a.inv_keep, &a.hash_base);
-  a.causal = causal;
-  a.relb = relb; a.relb_sh = relb_sh; a.relb_len = relb_len; a.rel_base = rel_base;
-  dim3 grid((Sq + 127) / 128, B * H);
-  if (p_drop > 0.f) {
-    if (causal) attn_fwd_d64_kernel<true, true, true><<<grid, 256, 0, stream>>>(a);
-    else attn_fwd_d64_kernel<true, false, true><<<grid, 256, 0, stream>>>(a);
-  } else {
-    if (causal) attn_fwd_d64_kernel<false, true, true><<<grid, 256, 0, stream>>>(a);
-    else attn_fwd_d64_kernel<false, false, true><<<grid, 256, 0, stream>>>(a);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -8;
-}
-
-// Head-dim-128 inference forward (attn_fwd_d128_kernel): the arguments of ct_attn_fwd without
-// dropout plus those of ct_attn_fwd_relbias; relb == nullptr selects the kernel without the
-// relative bias.  Rows are 128 elements, so the 32-bit offset check keeps 128 of slack.
-static inline bool fits32_d128(long rows, long row_stride) { return rows * row_stride + 128 < (1L << 31); }
-
-extern "C" int ct_attn_fwd_d128(const void* q, const long* qs, const void* k, const long* ks,
-                                const void* v, const long* vs, void* o, const long* os,
-                                const float* kbias, long kb_sb, const float* relb, long relb_sh,
-                                int relb_len, int rel_base, float* lse, int B, int H, int Sq, int Sk,
-                                float scale, int causal, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || (relb && relb_len <= 0)) return -1;
-  if (relb && relb_len > kRelBiasMax) return -4;
-  if (!fits32_d128(Sq, qs[1]) || !fits32_d128(Sk, ks[1]) || !fits32_d128(Sk, vs[1]) || !fits32_d128(Sq, os[1]))
-    return -5;
-  if (((uintptr_t)o & 15) || os[0] % 8 || os[1] % 8 || os[2] % 8) return -7;   // 16-byte output stores
-  AttnFwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
-  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.thr16 = 0; a.inv_keep = 1.f; a.hash_base = 0;
-  a.causal = causal;
-  a.relb = relb; a.relb_sh = relb ? relb_sh : 0; a.relb_len = relb ? relb_len : 0; a.rel_base = relb ? rel_base : 0;
-  dim3 grid((Sq + 127) / 128, B * H);
-  if (relb) {
-    const size_t dyn = (size_t)relb_len * sizeof(float);   // the relative-bias stage
-    if (causal) attn_fwd_d128_kernel<true, true><<<grid, 256, dyn, stream>>>(a);
-    else attn_fwd_d128_kernel<false, true><<<grid, 256, dyn, stream>>>(a);
-  } else {
-    if (causal) attn_fwd_d128_kernel<true, false><<<grid, 256, 0, stream>>>(a);
-    else attn_fwd_d128_kernel<false, false><<<grid, 256, 0, stream>>>(a);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -8;
-}
-
-// delta workspace: float[B*H*Sq]; dq_acc workspace: float[B*H*Sq*64] zeroed (only used
-// when Sk > 128)
-extern "C" int ct_attn_bwd(const void* q, const long* qs, const void* k, const long* ks,
-                           const void* v, const long* vs, const void* o, const long* os,
-                           const void* dO, const long* dos, void* dq, const long* dqs, void* dk,
-                           const long* dks, void* dv, const long* dvs, const float* kbias,
-                           long kb_sb, const float* lse, float* delta, float* dq_acc, int B, int H,
-                           int Sq, int Sk, float scale, float p_drop, uint64_t seed,
-                           uint64_t offset, int causal, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return -1;
-  if (p_drop > 0.f && (Sk % 2)) return -2;
-  if (!fits32(Sq, qs[1]) || !fits32(Sk, ks[1]) || !fits32(Sk, vs[1]) || !fits32(Sq, os[1]) ||
-      !fits32(Sq, dos[1]) || !fits32(Sq, dqs[1])) return -5;
-  // 16-byte dK / dV stores (store_row64)
-  if (((uintptr_t)dk & 15) || ((uintptr_t)dv & 15) || dks[0] % 8 || dks[1] % 8 || dks[2] % 8 || dvs[0] % 8 ||
-      dvs[1] % 8 || dvs[2] % 8)
-    return -7;
-  const long rows = (long)B * H * Sq;
-  AttnBwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.dO = (const bf16_t*)dO;
-  a.o = (const bf16_t*)o; a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
-  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.dq_acc = dq_acc;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.do_sb = dos[0]; a.do_ss = dos[1]; a.do_sh = dos[2];
-  a.dq_sb = dqs[0]; a.dq_ss = dqs[1]; a.dq_sh = dqs[2];
-  a.dk_sb = dks[0]; a.dk_ss = dks[1]; a.dk_sh = dks[2];
-  a.dv_sb = dvs[0]; a.dv_ss = dvs[1]; a.dv_sh = dvs[2];
-  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse; a.delta = delta;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
-  drop_params(p_drop, seed, offset, &a.thr16, &a.inv_keep, &a.hash_base);
-  a.causal = causal;
-  a.relb = nullptr; a.relb_sh = 0; a.relb_len = 0; a.rel_base = 0; a.drel_ws = nullptr;
-  const int nkb = (Sk + 127) / 128;
-  if (nkb > 1 && !dq_acc) return -3;
-  if (nkb > 1) hipMemsetAsync(dq_acc, 0, sizeof(float) * rows * 64, stream);
-  dim3 grid(nkb, B * H);
-  // causal masking is a template parameter (as in the forward): no per-element test of a
-  // runtime flag in the non-causal (BERT) kernel
-#define CT_ATTN_BWD(M, G)                                                                \
-  if (p_drop > 0.f) {                                                                    \
-    if (causal) attn_bwd_d64_kernel<true, true, M, G><<<grid, 256, 0, stream>>>(a);      \
-    else attn_bwd_d64_kernel<true, false, M, G><<<grid, 256, 0, stream>>>(a);            \
-  } else {                                                                               \
-    if (causal) attn_bwd_d64_kernel<false, true, M, G><<<grid, 256, 0, stream>>>(a);     \
-    else attn_bwd_d64_kernel<false, false, M, G><<<grid, 256, 0, stream>>>(a);           \
-  }
-  static const int bwd_gl = [] {
-    const char* e = getenv("CLOUDTIK_AMD_ATTN_BWD_GL");
-    return e ? atoi(e) : 1;
-  }();
-  if (nkb > 1) { CT_ATTN_BWD(true, false) }
-  else if (bwd_gl && Sq <= 128) { CT_ATTN_BWD(false, true) }
-  else { CT_ATTN_BWD(false, false) }
-#undef CT_ATTN_BWD
-  if (nkb > 1)
-    attn_dq_convert_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
-        dq_acc, (bf16_t*)dq, dqs[0], dqs[1], dqs[2], B, H, Sq);
-  return 0;
 }
 
 // Relative-bias backward.  W = 32 ceil(Sq / 32) + 127 offsets per workgroup window (see
@@ -1182,76 +948,190 @@ constexpr int kBwdRelMaxWindow = (160 * 1024 / 2 - 66048) / 8;
 extern "C" int ct_attn_bwd_relbias_window(int Sq) { return 32 * ((Sq + 31) / 32) + 127; }
 extern "C" int ct_attn_bwd_relbias_max_window() { return kBwdRelMaxWindow; }
 
-// ct_attn_bwd plus the relative-bias vector of the forward and its gradient: d_rel [H, relb_len]
-// fp32 (strides d_sh, d_si), every entry written.  drel_ws: float[B * nkb * H * W] workspace
-// (nkb = ceil(Sk / 128), W = ct_attn_bwd_relbias_window(Sq)), no need to clear it.  Dispatch:
-// Sk > 128 -> attn_bwd_d64_rel_kernel<DROP, CAUSAL, MULTI = true>, otherwise <.., MULTI = false>,
-// the register-staged single-block form for every Sq (REL has no LDS-DMA form), then
-// attn_drel_reduce_kernel.  rc -9: the windows would not leave room for two workgroups per CU.
-extern "C" int ct_attn_bwd_relbias(const void* q, const long* qs, const void* k, const long* ks,
-                                   const void* v, const long* vs, const void* o, const long* os,
-                                   const void* dO, const long* dos, void* dq, const long* dqs, void* dk,
-                                   const long* dks, void* dv, const long* dvs, const float* kbias,
-                                   long kb_sb, const float* relb, long relb_sh, int relb_len, int rel_base,
-                                   float* d_rel, long d_sh, long d_si, const float* lse, float* dq_acc,
-                                   float* drel_ws, int B, int H, int Sq, int Sk, float scale, float p_drop,
-                                   uint64_t seed, uint64_t offset, int causal, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || relb_len <= 0 || !relb || !d_rel || !drel_ws) return -1;
-  if (p_drop > 0.f && (Sk % 2)) return -2;
-  if (relb_len > kRelBiasMax) return -4;
-  if (rel_base < Sq - 1 || (long)rel_base + Sk > relb_len) return -10;   // relb must cover every offset
-  if (!fits32(Sq, qs[1]) || !fits32(Sk, ks[1]) || !fits32(Sk, vs[1]) || !fits32(Sq, os[1]) ||
-      !fits32(Sq, dos[1]) || !fits32(Sq, dqs[1])) return -5;
-  if (((uintptr_t)dk & 15) || ((uintptr_t)dv & 15) || dks[0] % 8 || dks[1] % 8 || dks[2] % 8 || dvs[0] % 8 ||
-      dvs[1] % 8 || dvs[2] % 8)
-    return -7;
-  const int W = ct_attn_bwd_relbias_window(Sq);
-  if (W > kBwdRelMaxWindow) return -9;
-  const long rows = (long)B * H * Sq;
-  AttnBwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.dO = (const bf16_t*)dO;
-  a.o = (const bf16_t*)o; a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
-  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.dq_acc = dq_acc;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.do_sb = dos[0]; a.do_ss = dos[1]; a.do_sh = dos[2];
-  a.dq_sb = dqs[0]; a.dq_ss = dqs[1]; a.dq_sh = dqs[2];
-  a.dk_sb = dks[0]; a.dk_ss = dks[1]; a.dk_sh = dks[2];
-  a.dv_sb = dvs[0]; a.dv_ss = dvs[1]; a.dv_sh = dvs[2];
-  a.kbias = kbias; a.kb_sb = kb_sb; a.lse = lse; a.delta = nullptr;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
-  drop_params(p_drop, seed, offset, &a.thr16, &a.inv_keep, &a.hash_base);
-  a.causal = causal;
-  a.relb = relb; a.relb_sh = relb_sh; a.relb_len = relb_len; a.rel_base = rel_base; a.drel_ws = drel_ws;
-  const int nkb = (Sk + 127) / 128;
-  if (nkb > 1 && !dq_acc) return -3;
-  if (nkb > 1) hipMemsetAsync(dq_acc, 0, sizeof(float) * rows * 64, stream);
-  dim3 grid(nkb, B * H);
-  const size_t dyn = (size_t)W * 2 * sizeof(float);
-#define CT_ATTN_BWD_REL(M)                                                                 \
-  if (p_drop > 0.f) {                                                                      \
-    if (causal) attn_bwd_d64_rel_kernel<true, true, M><<<grid, 256, dyn, stream>>>(a);     \
-    else attn_bwd_d64_rel_kernel<true, false, M><<<grid, 256, dyn, stream>>>(a);           \
-  } else {                                                                                 \
-    if (causal) attn_bwd_d64_rel_kernel<false, true, M><<<grid, 256, dyn, stream>>>(a);    \
-    else attn_bwd_d64_rel_kernel<false, false, M><<<grid, 256, dyn, stream>>>(a);          \
-  }
-  if (nkb > 1) { CT_ATTN_BWD_REL(true) } else { CT_ATTN_BWD_REL(false) }
-#undef CT_ATTN_BWD_REL
-  if (hipGetLastError() != hipSuccess) return -8;
-  if (nkb > 1)
-    attn_dq_convert_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
-        dq_acc, (bf16_t*)dq, dqs[0], dqs[1], dqs[2], B, H, Sq);
-  // window of key block 0 starts at offset 1 - 32 nq + rel_base = rel_base + 128 - W
-  attn_drel_reduce_kernel<<<(H * relb_len + 255) / 256, 256, 0, stream>>>(
-      drel_ws, d_rel, d_sh, d_si, B, nkb, H, W, relb_len, rel_base + 128 - W);
+// the kernels index rows inside one (batch, head) slice with 32-bit offsets; a row is D elements
+static bool fits32(const CtAttnView& t, long rows, int D) { return rows * t.ss + D < (1L << 31); }
+// 16-byte stores: o (the forwards' epilogue), dk / dv (store_row64)
+static bool aligned16(const CtAttnView& t) { return !(((uintptr_t)t.p & 15) || t.sb % 8 || t.ss % 8 || t.sh % 8); }
+
+// The refusals of ct_attn_fwd / ct_attn_bwd, in the order the codes are listed; every one comes
+// before the first memset or launch, so a refused call has written nothing.
+//    -1  a non-positive size, a D other than 64 (128: forward without dropout), or a missing
+//        pointer: lse for the d64 relative-bias forward, d_rel / drel_ws for the relative-bias
+//        backward; relb with relb_len <= 0
+//    -2  p > 0 with odd Sk (the dropout stream is drawn per element pair)
+//    -4  relb_len > kCtAttnRelBiasMax
+//   -10  backward: relb does not cover every (key - query) offset
+//    -5  a tensor's rows do not fit 32-bit offsets
+//    -7  o (forward) or dk / dv (backward) not 16-byte aligned
+//    -9  relative-bias backward: the windows would not leave room for two workgroups per CU
+//    -3  backward: Sk > 128 without dq_acc
+//    -6  forward, CLOUDTIK_AMD_ATTN_FWD_PIPE route only: item count (refused by ct_attn_fwd itself)
+//    -8  a launch or the memset failed (not a refusal: the stream may hold part of the call)
+static int attn_refusal(const CtAttnCall& c, bool bwd) {
+  const bool rel = c.relb != nullptr;
+  if (c.B <= 0 || c.H <= 0 || c.Sq <= 0 || c.Sk <= 0 || (rel && c.relb_len <= 0)) return -1;
+  if (c.D != 64 && (c.D != 128 || bwd || c.p_drop > 0.f)) return -1;
+  if (rel && (bwd ? !c.d_rel || !c.drel_ws : c.D == 64 && !c.lse)) return -1;
+  if (c.p_drop > 0.f && (c.Sk % 2)) return -2;
+  if (rel && c.relb_len > kCtAttnRelBiasMax) return -4;
+  if (bwd && rel && (c.rel_base < c.Sq - 1 || (long)c.rel_base + c.Sk > c.relb_len)) return -10;
+  if (!fits32(c.q, c.Sq, c.D) || !fits32(c.k, c.Sk, c.D) || !fits32(c.v, c.Sk, c.D) || !fits32(c.o, c.Sq, c.D))
+    return -5;
+  if (bwd && (!fits32(c.dO, c.Sq, c.D) || !fits32(c.dq, c.Sq, c.D))) return -5;
+  if (bwd ? !aligned16(c.dk) || !aligned16(c.dv) : !aligned16(c.o)) return -7;
+  if (bwd && rel && ct_attn_bwd_relbias_window(c.Sq) > kBwdRelMaxWindow) return -9;
+  if (bwd && c.Sk > 128 && !c.dq_acc) return -3;
   return 0;
 }
 
-extern "C" uint32_t ct_attn_hash_base(uint64_t seed, uint64_t offset) {
-  uint32_t t, b; float f;
-  drop_params(0.f, seed, offset, &t, &f, &b);
-  return b;
+// one tensor's pointer and strides into the kernel arguments, together
+template <class P>
+static void put(const CtAttnView& t, P*& p, long& sb, long& ss, long& sh) { p = (P*)t.p; sb = t.sb; ss = t.ss; sh = t.sh; }
+// The fields AttnFwdArgs and AttnBwdArgs share (two structs because each is its kernels' kernarg
+// layout).  Without relb its fields are zero; at p = 0 the dropout fields are drop_params(0, ..)'s.
+template <class Args>
+static void fill_shared(Args& a, const CtAttnCall& c) {
+  put(c.q, a.q, a.q_sb, a.q_ss, a.q_sh);
+  put(c.k, a.k, a.k_sb, a.k_ss, a.k_sh);
+  put(c.v, a.v, a.v_sb, a.v_ss, a.v_sh);
+  put(c.o, a.o, a.o_sb, a.o_ss, a.o_sh);
+  a.kbias = c.kbias; a.kb_sb = c.kb_sb; a.lse = c.lse;
+  a.B = c.B; a.H = c.H; a.Sq = c.Sq; a.Sk = c.Sk;
+  a.scale_log2 = c.scale * 1.4426950408889634f;
+  drop_params(c.p_drop, c.seed, c.offset, &a.thr16, &a.inv_keep, &a.hash_base);
+  a.causal = c.causal;
+  const bool rel = c.relb != nullptr;
+  a.relb = c.relb; a.relb_sh = rel ? c.relb_sh : 0; a.relb_len = rel ? c.relb_len : 0; a.rel_base = rel ? c.rel_base : 0;
 }
+
+// f(std::bool_constant<x>{}, std::bool_constant<y>{}): two runtime flags as template arguments
+// (masking and dropout are template parameters of every kernel: no per-element test of a runtime
+// flag in the non-causal, BERT, kernels)
+template <class F>
+static void with_bools(bool x, bool y, F&& f) {
+  if (x && y) f(std::true_type{}, std::true_type{});
+  else if (x) f(std::true_type{}, std::false_type{});
+  else if (y) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+template <int N> using int_c = std::integral_constant<int, N>;
+
+static int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : -8; }
+
+// Forward: writes o and lse (lse may be null without relb).  Dispatch:
+//   D 128           attn_fwd_d128_kernel<CAUSAL, REL> (inference: no dropout), the relative-bias stage in
+//                   dynamic LDS
+//   D 64, relb      attn_fwd_d64_kernel<DROP, CAUSAL, REL = true>, two workgroups per CU (T5: inference at
+//                   p = 0, training with the dropout stream of the plain forward)
+//   D 64            attn_fwd_d64_kernel<DROP, CAUSAL, false, WPE, GL>, or attn_fwd_pipe_kernel, by the knobs
+extern "C" int ct_attn_fwd(const CtAttnCall* call, hipStream_t stream) {
+  const CtAttnCall& c = *call;
+  if (const int rc = attn_refusal(c, false)) return rc;
+  AttnFwdArgs a;
+  fill_shared(a, c);
+  const dim3 grid((c.Sq + 127) / 128, c.B * c.H);
+  const bool drop = c.p_drop > 0.f, causal = c.causal != 0, rel = c.relb != nullptr;
+  if (c.D == 128) {
+    const size_t dyn = rel ? (size_t)c.relb_len * sizeof(float) : 0;
+    with_bools(causal, rel, [&](auto CA, auto RE) {
+      attn_fwd_d128_kernel<CA.value, RE.value><<<grid, 256, dyn, stream>>>(a);
+    });
+    return launch_rc();
+  }
+  if (rel) {
+    with_bools(drop, causal, [&](auto DR, auto CA) {
+      attn_fwd_d64_kernel<DR.value, CA.value, true><<<grid, 256, 0, stream>>>(a);
+    });
+    return launch_rc();
+  }
+  // default: 2 waves/SIMD.  (r3: 3 with dropout, 168 VGPRs, 74-75 vs 77-78 us per BERT-large
+  // layer; since both K/V tiles of an S <= 128 item load up front the 3-wave build spills one
+  // register and the BERT-large step is 0.03-0.06 ms faster at 2 in three interleaved rounds:
+  // 72.63 / 72.60 / 72.36 vs 72.57 / 72.55 / 72.34 ms)
+  static const int wpe_env = env_int("CLOUDTIK_AMD_ATTN_FWD_WPE", 0);
+  static const int gl = env_int("CLOUDTIK_AMD_ATTN_FWD_GLDS", 1);
+  const int wpe = (wpe_env >= 1 && wpe_env <= 4) ? wpe_env : (gl ? 3 : 2);
+  // opt-in: measured slower than the one-item kernel on BERT-large shapes (B 256, S 128,
+  // p 0.1: 75.5 us persistent / 84.9 us one item per workgroup vs 65.9 us;
+  // profiles/r3/attention_persistent_ab.md)
+  static const int pipe = env_int("CLOUDTIK_AMD_ATTN_FWD_PIPE", 0);
+  if (pipe) {
+    const long nitems = (long)grid.x * c.B * c.H;
+    if (nitems > (1L << 30)) return -6;
+    const int g1 = attn_persistent_grid(nitems, 2);
+    with_bools(drop, causal, [&](auto DR, auto CA) {
+      attn_fwd_pipe_kernel<DR.value, CA.value><<<g1, 256, 0, stream>>>(a);
+    });
+    return launch_rc();
+  }
+  auto launch = [&](auto W, auto G) {
+    with_bools(drop, causal, [&](auto DR, auto CA) {
+      attn_fwd_d64_kernel<DR.value, CA.value, false, W.value, G.value><<<grid, 256, 0, stream>>>(a);
+    });
+  };
+  if (gl) {
+    if (wpe == 4) launch(int_c<4>{}, std::true_type{});
+    else if (wpe == 3) launch(int_c<3>{}, std::true_type{});
+    else launch(int_c<2>{}, std::true_type{});
+  } else {
+    if (wpe == 3) launch(int_c<3>{}, std::false_type{});
+    else if (wpe == 1) launch(int_c<1>{}, std::false_type{});
+    else launch(int_c<2>{}, std::false_type{});
+  }
+  return launch_rc();
+}
+
+// Backward (D 64): writes dq, dk, dv and, with relb, every entry of d_rel.  Dispatch:
+//   no relb   attn_bwd_d64_kernel<DROP, CAUSAL, MULTI, GL>: Sk > 128 -> MULTI (dQ summed in dq_acc, zeroed
+//             here, then attn_dq_convert_kernel); otherwise one key block, by LDS DMA (GL) when Sq <= 128
+//             and CLOUDTIK_AMD_ATTN_BWD_GL is not 0
+//   relb      attn_bwd_d64_rel_kernel<DROP, CAUSAL, MULTI>: the register-staged single-block form for
+//             every Sq when Sk <= 128 (REL has no LDS-DMA form); two windows of dynamic LDS; then
+//             attn_drel_reduce_kernel sums the windows in drel_ws into d_rel
+extern "C" int ct_attn_bwd(const CtAttnCall* call, hipStream_t stream) {
+  const CtAttnCall& c = *call;
+  if (const int rc = attn_refusal(c, true)) return rc;
+  const bool drop = c.p_drop > 0.f, causal = c.causal != 0, rel = c.relb != nullptr;
+  AttnBwdArgs a;
+  fill_shared(a, c);
+  put(c.dO, a.dO, a.do_sb, a.do_ss, a.do_sh);
+  put(c.dq, a.dq, a.dq_sb, a.dq_ss, a.dq_sh);
+  put(c.dk, a.dk, a.dk_sb, a.dk_ss, a.dk_sh);
+  put(c.dv, a.dv, a.dv_sb, a.dv_ss, a.dv_sh);
+  a.dq_acc = c.dq_acc; a.scale = c.scale;
+  a.delta = rel ? nullptr : c.delta; a.drel_ws = rel ? c.drel_ws : nullptr;
+  const long rows = (long)c.B * c.H * c.Sq;
+  const int nkb = (c.Sk + 127) / 128, W = ct_attn_bwd_relbias_window(c.Sq);
+  const bool multi = nkb > 1;
+  if (multi && hipMemsetAsync(c.dq_acc, 0, sizeof(float) * rows * 64, stream) != hipSuccess) return -8;
+  const dim3 grid(nkb, c.B * c.H);
+  if (rel) {
+    const size_t dyn = (size_t)W * 2 * sizeof(float);
+    auto launch = [&](auto MU) {
+      with_bools(drop, causal, [&](auto DR, auto CA) {
+        attn_bwd_d64_rel_kernel<DR.value, CA.value, MU.value><<<grid, 256, dyn, stream>>>(a);
+      });
+    };
+    if (multi) launch(std::true_type{}); else launch(std::false_type{});
+  } else {
+    static const int bwd_gl = env_int("CLOUDTIK_AMD_ATTN_BWD_GL", 1);
+    auto launch = [&](auto MU, auto G) {
+      with_bools(drop, causal, [&](auto DR, auto CA) {
+        attn_bwd_d64_kernel<DR.value, CA.value, MU.value, G.value><<<grid, 256, 0, stream>>>(a);
+      });
+    };
+    if (multi) launch(std::true_type{}, std::false_type{});
+    else if (bwd_gl && c.Sq <= 128) launch(std::false_type{}, std::true_type{});
+    else launch(std::false_type{}, std::false_type{});
+  }
+  if (launch_rc()) return -8;
+  if (multi)
+    attn_dq_convert_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
+        c.dq_acc, a.dq, a.dq_sb, a.dq_ss, a.dq_sh, c.B, c.H, c.Sq);
+  // window of key block 0 starts at offset 1 - 32 nq + rel_base = rel_base + 128 - W
+  if (rel)
+    attn_drel_reduce_kernel<<<(c.H * c.relb_len + 255) / 256, 256, 0, stream>>>(
+        c.drel_ws, c.d_rel, c.d_sh, c.d_si, c.B, nkb, c.H, W, c.relb_len, c.rel_base + 128 - W);
+  return launch_rc();
+}
+

@@ -7,6 +7,7 @@
 #include <mutex>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
+#include "attention_api.h"   // the attention entries: declared once, for attention.hip too
 
 extern "C" {
 int ct_layernorm_fwd(const void*, const void*, const void*, const void*, const void*, void*, void*,
@@ -66,29 +67,6 @@ int ct_bn_bwd_given(const void*, const void*, const void*, const float*, void*, 
                     int, float*, int, int, hipStream_t);
 int ct_bn_bwd(const void*, const void*, const void*, const void*, const float*, void*, void*, void*, void*, int,
               float*, float*, int, int, int, hipStream_t);
-int ct_attn_fwd(const void*, const long*, const void*, const long*, const void*, const long*, void*,
-                const long*, const float*, long, float*, int, int, int, int, float, float, uint64_t,
-                uint64_t, int, hipStream_t);
-int ct_attn_fwd_relbias(const void*, const long*, const void*, const long*, const void*, const long*, void*,
-                        const long*, const float*, long, const float*, long, int, int, float*, int, int, int, int,
-                        float, int, hipStream_t);
-int ct_attn_fwd_d128(const void*, const long*, const void*, const long*, const void*, const long*, void*,
-                     const long*, const float*, long, const float*, long, int, int, float*, int, int, int, int,
-                     float, int, hipStream_t);
-int ct_attn_bwd(const void*, const long*, const void*, const long*, const void*, const long*,
-                const void*, const long*, const void*, const long*, void*, const long*, void*,
-                const long*, void*, const long*, const float*, long, const float*, float*, float*,
-                int, int, int, int, float, float, uint64_t, uint64_t, int, hipStream_t);
-int ct_attn_fwd_relbias_train(const void*, const long*, const void*, const long*, const void*, const long*, void*,
-                              const long*, const float*, long, const float*, long, int, int, float*, int, int, int,
-                              int, float, float, uint64_t, uint64_t, int, hipStream_t);
-int ct_attn_bwd_relbias_window(int);
-int ct_attn_bwd_relbias_max_window();
-int ct_attn_bwd_relbias(const void*, const long*, const void*, const long*, const void*, const long*,
-                        const void*, const long*, const void*, const long*, void*, const long*, void*,
-                        const long*, void*, const long*, const float*, long, const float*, long, int, int,
-                        float*, long, long, const float*, float*, float*, int, int, int, int, float, float,
-                        uint64_t, uint64_t, int, hipStream_t);
 }
 
 #define CHECK_CUDA(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")
@@ -436,162 +414,124 @@ std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor dlogits, int64_t 
 // ---------------------------------------------------------------- attention (head_dim 64 / 128)
 // q, k, v, o: 4-D [B, S, H, D] views with unit stride on the last dim (e.g. slices of a
 // packed [B, S, 3, H, D] QKV projection output); key_bias: fp32 [B, Sk] additive.
-// The forward takes D = 64 or D = 128 (the d128 kernel: inference only); the backward D = 64.
-static void bshd_strides_fwd(const at::Tensor& t, long* st, const char* name) {
-  TORCH_CHECK(t.dim() == 4 && (t.size(3) == 64 || t.size(3) == 128) && t.stride(3) == 1, name,
-              " must be [B,S,H,64] or [B,S,H,128] with unit last stride");
+// The forward takes D = 64 or D = 128 (the d128 kernel: inference only); the training forward and
+// the backwards D = 64.  Every function fills one CtAttnCall (attention_api.h) through the helpers
+// below, each tensor's pointer and strides together, and calls ct_attn_fwd or ct_attn_bwd.
+static CtAttnView attn_view(const at::Tensor& t, const char* name, bool d128) {
+  TORCH_CHECK(t.dim() == 4 && (t.size(3) == 64 || (d128 && t.size(3) == 128)) && t.stride(3) == 1, name,
+              d128 ? " must be [B,S,H,64] or [B,S,H,128] with unit last stride"
+                   : " must be [B,S,H,64] with unit last stride (the head-dim-128 kernel is forward only)");
   CHECK_CUDA(t); CHECK_BF16(t);
-  st[0] = t.stride(0); st[1] = t.stride(1); st[2] = t.stride(2);
+  return {t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)};
 }
-static void bshd_strides_bwd(const at::Tensor& t, long* st, const char* name) {
-  TORCH_CHECK(t.dim() == 4 && t.size(3) == 64 && t.stride(3) == 1, name,
-              " must be [B,S,H,64] with unit last stride (the head-dim-128 kernel is forward only)");
-  CHECK_CUDA(t); CHECK_BF16(t);
-  st[0] = t.stride(0); st[1] = t.stride(1); st[2] = t.stride(2);
-}
-// the head dim the forward dispatches on: q, k, v and o must agree
-static int fwd_head_dim(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o) {
+// The views and sizes of a call: q, k, v, o (D = 128 allowed when d128) and, for a backward, their
+// gradients dO, dq, dk, dv.  Everything else in the descriptor is left null / zero.
+static CtAttnCall attn_call(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
+                            bool d128, const at::Tensor* dO = nullptr, const at::Tensor* dq = nullptr,
+                            const at::Tensor* dk = nullptr, const at::Tensor* dv = nullptr) {
+  CtAttnCall c{};
+  c.q = attn_view(q, "q", d128); c.k = attn_view(k, "k", d128); c.v = attn_view(v, "v", d128); c.o = attn_view(o, "o", d128);
+  if (dO) {
+    c.dO = attn_view(*dO, "dO", false); c.dq = attn_view(*dq, "dq", false);
+    c.dk = attn_view(*dk, "dk", false); c.dv = attn_view(*dv, "dv", false);
+  }
+  // the head dim the forward dispatches on: q, k, v and o must agree
   const long D = q.size(3);
   TORCH_CHECK(k.size(3) == D && v.size(3) == D && o.size(3) == D, "q, k, v and o must have the same head dim, got ",
               D, ", ", k.size(3), ", ", v.size(3), ", ", o.size(3));
-  return (int)D;
+  if (dO) {
+    TORCH_CHECK(dO->sizes() == o.sizes() && dq->sizes() == q.sizes() && dk->sizes() == k.sizes() && dv->sizes() == v.sizes());
+  }
+  c.B = q.size(0); c.Sq = q.size(1); c.H = q.size(2); c.Sk = k.size(1); c.D = (int)D;
+  TORCH_CHECK(k.size(0) == c.B && v.size(0) == c.B && k.size(2) == c.H && v.size(2) == c.H && v.size(1) == c.Sk);
+  TORCH_CHECK(o.size(0) == c.B && o.size(1) == c.Sq && o.size(2) == c.H);
+  return c;
+}
+static void key_bias_checked(const c10::optional<at::Tensor>& key_bias, CtAttnCall& c) {
+  if (!(key_bias.has_value() && key_bias->defined())) return;
+  CHECK_F32(*key_bias); CHECK_CUDA(*key_bias);
+  TORCH_CHECK(key_bias->dim() == 2 && key_bias->size(0) == c.B && key_bias->size(1) == c.Sk && key_bias->stride(1) == 1);
+  c.kbias = key_bias->data_ptr<float>(); c.kb_sb = key_bias->stride(0);
+}
+// T5-style relative-position bias vector relb [H, L]; returns L
+static long relb_checked(const at::Tensor& relb, int64_t rel_base, CtAttnCall& c) {
+  CHECK_F32(relb); CHECK_CUDA(relb);
+  TORCH_CHECK(relb.dim() == 2 && relb.size(0) == c.H && (relb.stride(1) == 1 || relb.size(1) == 1),
+              "relb must be [H, L] fp32");
+  const long L = relb.size(1);
+  TORCH_CHECK(rel_base >= c.Sq - 1 && rel_base + c.Sk <= L, "relb does not cover every (key - query) offset");
+  c.relb = relb.data_ptr<float>(); c.relb_sh = relb.stride(0); c.rel_base = (int)rel_base;
+  c.relb_len = (int)std::min<long>(L, 1 << 20);   // past the limit either way: the entry answers rc=-4
+  return L;
+}
+// the kernels read lse as a dense fp32 [B*H, Sq]
+static void lse_checked(const at::Tensor& lse, CtAttnCall& c) {
+  CHECK_F32(lse); CHECK_CUDA(lse);
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == (long)c.B * c.H * c.Sq, "lse must be contiguous fp32 [B*H, Sq]");
+  c.lse = lse.data_ptr<float>();
+}
+static void attn_params(CtAttnCall& c, double scale, double p, int64_t seed, int64_t offset, bool causal) {
+  c.scale = (float)scale; c.p_drop = (float)p; c.seed = (uint64_t)seed; c.offset = (uint64_t)offset;
+  c.causal = causal ? 1 : 0;
+}
+// allocates lse, runs the forward; returns lse
+static at::Tensor attn_fwd_run(CtAttnCall& c, const at::Tensor& q, const char* who) {
+  auto lse = at::empty({(long)c.B * c.H, c.Sq}, q.options().dtype(at::kFloat));
+  c.lse = lse.data_ptr<float>();
+  int rc = ct_attn_fwd(&c, cur_stream());
+  TORCH_CHECK(rc == 0, who, c.D == 128 ? " (head dim 128)" : "", " failed rc=", rc);
+  return lse;
 }
 
 at::Tensor attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                     c10::optional<at::Tensor> key_bias, double scale, double p, int64_t seed,
                     int64_t offset, bool causal) {
-  long qs[3], ks[3], vs[3], os[3];
-  bshd_strides_fwd(q, qs, "q"); bshd_strides_fwd(k, ks, "k"); bshd_strides_fwd(v, vs, "v"); bshd_strides_fwd(o, os, "o");
-  const int D = fwd_head_dim(q, k, v, o);
-  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
-  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
-  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
-  const float* kb = nullptr; long kb_sb = 0;
-  if (key_bias.has_value() && key_bias->defined()) {
-    CHECK_F32(*key_bias); CHECK_CUDA(*key_bias);
-    TORCH_CHECK(key_bias->dim() == 2 && key_bias->size(0) == B && key_bias->size(1) == Sk && key_bias->stride(1) == 1);
-    kb = key_bias->data_ptr<float>(); kb_sb = key_bias->stride(0);
-  }
-  auto lse = at::empty({(long)B * H, Sq}, q.options().dtype(at::kFloat));
-  if (D == 128) {
-    TORCH_CHECK(p == 0.0, "attn_fwd: the head-dim-128 kernel has no dropout (p must be 0)");
-    int rc = ct_attn_fwd_d128(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
-                              nullptr, 0, 0, 0, lse.data_ptr<float>(), B, H, Sq, Sk, (float)scale, causal ? 1 : 0,
-                              cur_stream());
-    TORCH_CHECK(rc == 0, "attn_fwd (head dim 128) failed rc=", rc);
-    return lse;
-  }
-  int rc = ct_attn_fwd(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
-                       lse.data_ptr<float>(), B, H, Sq, Sk, (float)scale, (float)p, (uint64_t)seed,
-                       (uint64_t)offset, causal ? 1 : 0, cur_stream());
-  TORCH_CHECK(rc == 0, "attn_fwd failed rc=", rc);
-  return lse;
+  CtAttnCall c = attn_call(q, k, v, o, true);
+  key_bias_checked(key_bias, c);
+  TORCH_CHECK(c.D == 64 || p == 0.0, "attn_fwd: the head-dim-128 kernel has no dropout (p must be 0)");
+  // D = 128: no dropout stream, so no seed either
+  attn_params(c, scale, p, c.D == 64 ? seed : 0, c.D == 64 ? offset : 0, causal);
+  return attn_fwd_run(c, q, "attn_fwd");
 }
 
 // inference forward with a T5-style relative-position bias vector relb [H, L]
 at::Tensor attn_fwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                             c10::optional<at::Tensor> key_bias, at::Tensor relb, int64_t rel_base, double scale,
                             bool causal) {
-  long qs[3], ks[3], vs[3], os[3];
-  bshd_strides_fwd(q, qs, "q"); bshd_strides_fwd(k, ks, "k"); bshd_strides_fwd(v, vs, "v"); bshd_strides_fwd(o, os, "o");
-  const int D = fwd_head_dim(q, k, v, o);
-  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
-  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
-  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
-  CHECK_F32(relb); CHECK_CUDA(relb);
-  TORCH_CHECK(relb.dim() == 2 && relb.size(0) == H && (relb.stride(1) == 1 || relb.size(1) == 1),
-              "relb must be [H, L] fp32");
-  const long L = relb.size(1);
-  TORCH_CHECK(rel_base >= Sq - 1 && rel_base + Sk <= L, "relb does not cover every (key - query) offset");
-  const float* kb = nullptr; long kb_sb = 0;
-  if (key_bias.has_value() && key_bias->defined()) {
-    CHECK_F32(*key_bias); CHECK_CUDA(*key_bias);
-    TORCH_CHECK(key_bias->dim() == 2 && key_bias->size(0) == B && key_bias->size(1) == Sk && key_bias->stride(1) == 1);
-    kb = key_bias->data_ptr<float>(); kb_sb = key_bias->stride(0);
-  }
-  auto lse = at::empty({(long)B * H, Sq}, q.options().dtype(at::kFloat));
-  if (D == 128) {
-    int rc = ct_attn_fwd_d128(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
-                              relb.data_ptr<float>(), relb.stride(0), (int)L, (int)rel_base, lse.data_ptr<float>(),
-                              B, H, Sq, Sk, (float)scale, causal ? 1 : 0, cur_stream());
-    TORCH_CHECK(rc == 0, "attn_fwd_relbias (head dim 128) failed rc=", rc);
-    return lse;
-  }
-  int rc = ct_attn_fwd_relbias(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb, kb_sb,
-                               relb.data_ptr<float>(), relb.stride(0), (int)L, (int)rel_base, lse.data_ptr<float>(),
-                               B, H, Sq, Sk, (float)scale, causal ? 1 : 0, cur_stream());
-  TORCH_CHECK(rc == 0, "attn_fwd_relbias failed rc=", rc);
-  return lse;
+  CtAttnCall c = attn_call(q, k, v, o, true);
+  relb_checked(relb, rel_base, c);
+  key_bias_checked(key_bias, c);
+  attn_params(c, scale, 0.0, 0, 0, causal);
+  return attn_fwd_run(c, q, "attn_fwd_relbias");
 }
 
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dO, at::Tensor dq,
               at::Tensor dk, at::Tensor dv, c10::optional<at::Tensor> key_bias, at::Tensor lse,
               double scale, double p, int64_t seed, int64_t offset, bool causal) {
-  long qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
-  bshd_strides_bwd(q, qs, "q"); bshd_strides_bwd(k, ks, "k"); bshd_strides_bwd(v, vs, "v"); bshd_strides_bwd(o, os, "o");
-  bshd_strides_bwd(dO, dos, "dO"); bshd_strides_bwd(dq, dqs, "dq"); bshd_strides_bwd(dk, dks, "dk"); bshd_strides_bwd(dv, dvs, "dv");
-  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
-  TORCH_CHECK(dO.sizes() == o.sizes() && dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes());
-  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
-  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
-  // the kernels read lse as a dense fp32 [B*H, Sq] and key_bias as fp32 rows of Sk keys
-  CHECK_F32(lse); CHECK_CUDA(lse);
-  TORCH_CHECK(lse.is_contiguous() && lse.numel() == (long)B * H * Sq, "lse must be contiguous fp32 [B*H, Sq]");
-  const float* kb = nullptr; long kb_sb = 0;
-  if (key_bias.has_value() && key_bias->defined()) {
-    CHECK_F32(*key_bias); CHECK_CUDA(*key_bias);
-    TORCH_CHECK(key_bias->dim() == 2 && key_bias->size(0) == B && key_bias->size(1) == Sk && key_bias->stride(1) == 1);
-    kb = key_bias->data_ptr<float>(); kb_sb = key_bias->stride(0);
-  }
+  CtAttnCall c = attn_call(q, k, v, o, false, &dO, &dq, &dk, &dv);
+  lse_checked(lse, c);
+  key_bias_checked(key_bias, c);
+  attn_params(c, scale, p, seed, offset, causal);
   auto fo = q.options().dtype(at::kFloat);
-  auto delta = at::empty({(long)B * H * Sq}, fo);
+  auto delta = at::empty({(long)c.B * c.H * c.Sq}, fo);
   at::Tensor dq_acc;
-  if (Sk > 128) dq_acc = at::empty({(long)B * H * Sq * 64}, fo);
-  int rc = ct_attn_bwd(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, dO.data_ptr(), dos,
-                       dq.data_ptr(), dqs, dk.data_ptr(), dks, dv.data_ptr(), dvs, kb, kb_sb,
-                       lse.data_ptr<float>(), delta.data_ptr<float>(), Sk > 128 ? dq_acc.data_ptr<float>() : nullptr,
-                       B, H, Sq, Sk, (float)scale, (float)p, (uint64_t)seed, (uint64_t)offset,
-                       causal ? 1 : 0, cur_stream());
+  if (c.Sk > 128) dq_acc = at::empty({(long)c.B * c.H * c.Sq * 64}, fo);
+  c.delta = delta.data_ptr<float>();
+  c.dq_acc = c.Sk > 128 ? dq_acc.data_ptr<float>() : nullptr;
+  int rc = ct_attn_bwd(&c, cur_stream());
   TORCH_CHECK(rc == 0, "attn_bwd failed rc=", rc);
 }
 
 // ---- relative-bias attention for training (T5, head dim 64): forward with dropout + lse, and a
 // backward that also returns the gradient of the bias vector
-static const float* relb_checked(const at::Tensor& relb, int H, int Sq, int Sk, int64_t rel_base, long* L) {
-  CHECK_F32(relb); CHECK_CUDA(relb);
-  TORCH_CHECK(relb.dim() == 2 && relb.size(0) == H && (relb.stride(1) == 1 || relb.size(1) == 1),
-              "relb must be [H, L] fp32");
-  *L = relb.size(1);
-  TORCH_CHECK(rel_base >= Sq - 1 && rel_base + Sk <= *L, "relb does not cover every (key - query) offset");
-  return relb.data_ptr<float>();
-}
-static const float* key_bias_checked(const c10::optional<at::Tensor>& key_bias, int B, int Sk, long* kb_sb) {
-  *kb_sb = 0;
-  if (!(key_bias.has_value() && key_bias->defined())) return nullptr;
-  CHECK_F32(*key_bias); CHECK_CUDA(*key_bias);
-  TORCH_CHECK(key_bias->dim() == 2 && key_bias->size(0) == B && key_bias->size(1) == Sk && key_bias->stride(1) == 1);
-  *kb_sb = key_bias->stride(0);
-  return key_bias->data_ptr<float>();
-}
-
 at::Tensor attn_fwd_relbias_train(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                   c10::optional<at::Tensor> key_bias, at::Tensor relb, int64_t rel_base,
                                   double scale, double p, int64_t seed, int64_t offset, bool causal) {
-  long qs[3], ks[3], vs[3], os[3];
-  bshd_strides_bwd(q, qs, "q"); bshd_strides_bwd(k, ks, "k"); bshd_strides_bwd(v, vs, "v"); bshd_strides_bwd(o, os, "o");
-  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
-  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
-  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
-  long L, kb_sb;
-  const float* rp = relb_checked(relb, H, Sq, Sk, rel_base, &L);
-  const float* kb = key_bias_checked(key_bias, B, Sk, &kb_sb);
-  auto lse = at::empty({(long)B * H, Sq}, q.options().dtype(at::kFloat));
-  int rc = ct_attn_fwd_relbias_train(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, kb,
-                                     kb_sb, rp, relb.stride(0), (int)std::min<long>(L, 1 << 20), (int)rel_base,
-                                     lse.data_ptr<float>(), B, H, Sq, Sk, (float)scale, (float)p, (uint64_t)seed,
-                                     (uint64_t)offset, causal ? 1 : 0, cur_stream());
-  TORCH_CHECK(rc == 0, "attn_fwd_relbias_train failed rc=", rc);
-  return lse;
+  CtAttnCall c = attn_call(q, k, v, o, false);
+  relb_checked(relb, rel_base, c);
+  key_bias_checked(key_bias, c);
+  attn_params(c, scale, p, seed, offset, causal);
+  return attn_fwd_run(c, q, "attn_fwd_relbias_train");
 }
 
 // d_rel: fp32 [H, L] in any strides (the gradient in the layout of the caller's bias view); every
@@ -600,36 +540,26 @@ void attn_bwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at
                       at::Tensor dk, at::Tensor dv, at::Tensor d_rel, c10::optional<at::Tensor> key_bias,
                       at::Tensor relb, int64_t rel_base, at::Tensor lse, double scale, double p, int64_t seed,
                       int64_t offset, bool causal) {
-  long qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
-  bshd_strides_bwd(q, qs, "q"); bshd_strides_bwd(k, ks, "k"); bshd_strides_bwd(v, vs, "v"); bshd_strides_bwd(o, os, "o");
-  bshd_strides_bwd(dO, dos, "dO"); bshd_strides_bwd(dq, dqs, "dq"); bshd_strides_bwd(dk, dks, "dk"); bshd_strides_bwd(dv, dvs, "dv");
-  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
-  TORCH_CHECK(dO.sizes() == o.sizes() && dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes());
-  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Sk);
-  TORCH_CHECK(o.size(0) == B && o.size(1) == Sq && o.size(2) == H);
-  CHECK_F32(lse); CHECK_CUDA(lse);
-  TORCH_CHECK(lse.is_contiguous() && lse.numel() == (long)B * H * Sq, "lse must be contiguous fp32 [B*H, Sq]");
-  long L, kb_sb;
-  const float* rp = relb_checked(relb, H, Sq, Sk, rel_base, &L);
-  const float* kb = key_bias_checked(key_bias, B, Sk, &kb_sb);
+  CtAttnCall c = attn_call(q, k, v, o, false, &dO, &dq, &dk, &dv);
+  lse_checked(lse, c);
+  const long L = relb_checked(relb, rel_base, c);
+  key_bias_checked(key_bias, c);
+  attn_params(c, scale, p, seed, offset, causal);
   CHECK_F32(d_rel); CHECK_CUDA(d_rel);
-  TORCH_CHECK(d_rel.dim() == 2 && d_rel.size(0) == H && d_rel.size(1) == L, "d_rel must be fp32 [H, L] like relb");
-  TORCH_CHECK(L <= 1 || H <= 1 || (d_rel.stride(0) != 0 && d_rel.stride(1) != 0), "d_rel must not be an expanded view");
+  TORCH_CHECK(d_rel.dim() == 2 && d_rel.size(0) == c.H && d_rel.size(1) == L, "d_rel must be fp32 [H, L] like relb");
+  TORCH_CHECK(L <= 1 || c.H <= 1 || (d_rel.stride(0) != 0 && d_rel.stride(1) != 0), "d_rel must not be an expanded view");
+  c.d_rel = d_rel.data_ptr<float>(); c.d_sh = d_rel.stride(0); c.d_si = d_rel.stride(1);
   auto fo = q.options().dtype(at::kFloat);
-  const int nkb = (Sk + 127) / 128;
-  const long W = ct_attn_bwd_relbias_window(Sq);
+  const int nkb = (c.Sk + 127) / 128;
+  const long W = ct_attn_bwd_relbias_window(c.Sq);
   at::Tensor dq_acc, ws;
-  // the C entry refuses L > 4096 and windows past the LDS budget before it touches a workspace
-  const bool sized = L <= 4096 && W <= ct_attn_bwd_relbias_max_window();
-  if (Sk > 128 && sized) dq_acc = at::empty({(long)B * H * Sq * 64}, fo);
-  ws = at::empty({sized ? (long)B * nkb * H * W : 1L}, fo);
-  int rc = ct_attn_bwd_relbias(q.data_ptr(), qs, k.data_ptr(), ks, v.data_ptr(), vs, o.data_ptr(), os, dO.data_ptr(),
-                               dos, dq.data_ptr(), dqs, dk.data_ptr(), dks, dv.data_ptr(), dvs, kb, kb_sb, rp,
-                               relb.stride(0), (int)std::min<long>(L, 1 << 20), (int)rel_base,
-                               d_rel.data_ptr<float>(), d_rel.stride(0), d_rel.stride(1), lse.data_ptr<float>(),
-                               dq_acc.defined() ? dq_acc.data_ptr<float>() : nullptr, ws.data_ptr<float>(), B, H, Sq,
-                               Sk, (float)scale, (float)p, (uint64_t)seed, (uint64_t)offset, causal ? 1 : 0,
-                               cur_stream());
+  // the C entry refuses a longer L and windows past the LDS budget before it touches a workspace
+  const bool sized = L <= kCtAttnRelBiasMax && W <= ct_attn_bwd_relbias_max_window();
+  if (c.Sk > 128 && sized) dq_acc = at::empty({(long)c.B * c.H * c.Sq * 64}, fo);
+  ws = at::empty({sized ? (long)c.B * nkb * c.H * W : 1L}, fo);
+  c.dq_acc = dq_acc.defined() ? dq_acc.data_ptr<float>() : nullptr;
+  c.drel_ws = ws.data_ptr<float>();
+  int rc = ct_attn_bwd(&c, cur_stream());
   TORCH_CHECK(rc == 0, "attn_bwd_relbias failed rc=", rc);
 }
 

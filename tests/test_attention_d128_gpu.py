@@ -328,25 +328,27 @@ def _padded_out(dev, B, S, H, hs):
 @pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
 @pytest.mark.parametrize("Sq,Sk", [(100, 72), (33, 130)])
 def test_strided_views(cuda, Sq, Sk, causal):
-    """K and V are a [B, T, H, D] cache sliced to Sk, q comes out of a packed [B, Sq, 3, H, D]
-    projection, o is a padded view.  Everything outside the views holds a NaN sentinel: results
+    """K and V are slices of two caches of different lengths and head counts, q comes out of a
+    packed [B, Sq, 3, H, D] projection, o is a padded view.  Everything outside the views holds a NaN sentinel: results
     stay within bounds (so no padding was read into them) and no sentinel changes."""
     inp = _inputs(B0, H0, Sq, Sk)
     kb = _key_bias(B0, Sk, "present")
     g = torch.Generator().manual_seed(15 + Sq)
     relv = torch.randn(H0, Sq + Sk - 1, generator=g) * 0.5
     C = ops.require_native()
-    T = Sk + 5
-    kc, vc = _sentinel(cuda, B0, T, H0, D), _sentinel(cuda, B0, T, H0, D)
+    # the V cache is longer and has one head more than the K cache, so q, k, v and o have four
+    # different (batch, row, head) stride triples: one tensor's strides used for another show
+    kc, vc = _sentinel(cuda, B0, Sk + 5, H0, D), _sentinel(cuda, B0, Sk + 9, H0 + 1, D)
     kc[:, :Sk] = _bshd(inp["k"], cuda)
-    vc[:, :Sk] = _bshd(inp["v"], cuda)
+    vc[:, :Sk, :H0] = _bshd(inp["v"], cuda)
     packed = _sentinel(cuda, B0, Sq, 3, H0, D)
     packed[:, :, 0] = _bshd(inp["q"], cuda)
-    q, k, v = packed.view(B0, Sq, 3 * H0 * D).view(B0, Sq, 3, H0, D)[:, :, 0], kc[:, :Sk], vc[:, :Sk]
+    q, k, v = packed.view(B0, Sq, 3 * H0 * D).view(B0, Sq, 3, H0, D)[:, :, 0], kc[:, :Sk], vc[:, :Sk, :H0]
     snap = [t.clone() for t in (kc, vc, packed)]
     for rel in (False, True):
         want = _ref64(inp, kb, causal, _rel_matrix(relv, Sq - 1, Sq, Sk) if rel else None)
         buf, o, mask = _padded_out(cuda, B0, Sq, H0, 136)
+        assert len({t.stride()[:3] for t in (q, k, v, o)}) == 4
         lse = _call(C, q, k, v, o, kb.to(cuda), relv.to(cuda) if rel else None, Sq - 1, SCALE, causal)
         torch.cuda.synchronize()
         assert _untouched(buf, mask), "o: written outside its valid region"

@@ -511,11 +511,13 @@ def test_odd_sk_dropout_routes_to_reference(cuda, Sq, Sk):
 
 # ------------------------------------------------------------------ 3. views, padding, refusals
 SENTINEL = 0x7FA5      # a bf16 NaN bit pattern no kernel produces
+# head strides of the padded-view tests: all different, multiples of 8 (16-byte rows), none 64
+PAD_HS = {"q": 72, "k": 80, "v": 88, "do": 96, "o": 104, "dq": 112, "dk": 120, "dv": 136}
 
 
 def _padded(dev, B, S, H, hs, fill_bits=SENTINEL, data=None):
-    """A [B, S, H, 64] view into a larger buffer: 3 extra rows after S, head stride hs (72 or 80,
-    not 64), a 16-element gap between batches, an 8-element (16-byte) offset from the base.
+    """A [B, S, H, 64] view into a larger buffer: 3 extra rows after S, head stride hs (a multiple
+    of 8, not 64), a 16-element gap between batches, an 8-element (16-byte) offset from the base.
     Returns (buffer, view, mask of the buffer elements the view covers)."""
     ss = H * hs
     sb = (S + 3) * ss + 16
@@ -539,16 +541,17 @@ def _untouched(buf, mask, bits=SENTINEL):
 @pytest.mark.parametrize("Sq,Sk", [(100, 72), (160, 264)])
 def test_padded_views_write_nothing_outside(cuda, Sq, Sk, causal):
     """Every tensor is a padded view (rows after S, gaps between heads and batches); the inputs'
-    padding is NaN, the outputs' a sentinel that must survive bit for bit."""
+    padding is NaN, the outputs' a sentinel that must survive bit for bit.  The eight tensors have
+    eight different head strides (PAD_HS), hence eight different stride triples: a launch that
+    takes one tensor's strides for another's reads NaN padding or writes over a sentinel."""
     case = (Sq, Sk, causal, 0.1, "present")
     inp, kb, keep, (seed, off), want = _expected(case)
     C = ops.require_native()
     nan = 0x7FC0
     t = {}
-    for n, S, hs in (("q", Sq, 72), ("k", Sk, 80), ("v", Sk, 72), ("do", Sq, 80)):
-        _, t[n], _ = _padded(cuda, B0, S, H0, hs, nan, inp[n].to(cuda).transpose(1, 2))
-    out = {n: _padded(cuda, B0, S, H0, hs) for n, S, hs in (("o", Sq, 72), ("dq", Sq, 80), ("dk", Sk, 72),
-                                                            ("dv", Sk, 80))}
+    for n, S in (("q", Sq), ("k", Sk), ("v", Sk), ("do", Sq)):
+        _, t[n], _ = _padded(cuda, B0, S, H0, PAD_HS[n], nan, inp[n].to(cuda).transpose(1, 2))
+    out = {n: _padded(cuda, B0, S, H0, PAD_HS[n]) for n, S in (("o", Sq), ("dq", Sq), ("dk", Sk), ("dv", Sk))}
     kbd = kb.to(cuda)
     lse = C.attn_fwd(t["q"], t["k"], t["v"], out["o"][1], kbd, SCALE, 0.1, seed, off, causal)
     C.attn_bwd(t["q"], t["k"], t["v"], out["o"][1], t["do"], out["dq"][1], out["dk"][1], out["dv"][1], kbd, lse,

@@ -79,6 +79,7 @@ import torch
 from cloudtik_amd import ops
 from cloudtik_amd.ops import reference as ref
 from cloudtik_amd.ops.attention import _relbias_reference
+from test_attention_gpu import PAD_HS, _padded, _untouched
 
 D = 64
 B0, H0 = 2, 3
@@ -521,6 +522,34 @@ def test_transposed_rel_view(cuda, Sq, Sk):
     C.attn_bwd_relbias(q, k, v, o, do, outs[0], outs[1], outs[2], d_t, kb.to(cuda), relc, rel_base, lse, SCALE, 0.1,
                        seed, off, True)
     _check({"d_rel": d_t.cpu()}, want, None, "strided d_rel " + _id(case), True, 0.1, rel_base)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Sq,Sk", [(100, 72), (160, 264)])
+def test_padded_views_distinct_strides(cuda, Sq, Sk):
+    """test_attention_gpu.py's test_padded_views_write_nothing_outside for the relative-bias pair:
+    q, k, v, dO, o, dq, dk, dv are padded views with eight different head strides (PAD_HS), the
+    inputs' padding NaN, the outputs' a sentinel that must survive; d_rel is a transposed [L, H]
+    view filled with NaN.  Strides of one tensor used for another read NaN or hit a sentinel."""
+    case = (Sq, Sk, True, 0.1, "present")
+    inp, kb, rel, rel_base, keep, (seed, off), want = _expected(case)
+    C = ops.require_native()
+    t = {}
+    for n, S in (("q", Sq), ("k", Sk), ("v", Sk), ("do", Sq)):
+        _, t[n], _ = _padded(cuda, B0, S, H0, PAD_HS[n], 0x7FC0, _bshd(inp[n], cuda))
+    out = {n: _padded(cuda, B0, S, H0, PAD_HS[n]) for n, S in (("o", Sq), ("dq", Sq), ("dk", Sk), ("dv", Sk))}
+    assert len({v.stride()[:3] for v in list(t.values()) + [view for _, view, _ in out.values()]}) == 8
+    kbd, reld = kb.to(cuda), rel.to(cuda)
+    d_rel = torch.full((rel.shape[1], H0), float("nan"), device=cuda).t()
+    lse = C.attn_fwd_relbias_train(t["q"], t["k"], t["v"], out["o"][1], kbd, reld, rel_base, SCALE, 0.1, seed, off, True)
+    C.attn_bwd_relbias(t["q"], t["k"], t["v"], out["o"][1], t["do"], out["dq"][1], out["dk"][1], out["dv"][1], d_rel,
+                       kbd, reld, rel_base, lse, SCALE, 0.1, seed, off, True)
+    torch.cuda.synchronize()
+    for n, (buf, _, mask) in out.items():
+        assert _untouched(buf, mask), "%s: written outside its valid region" % n
+    got = {n: _back(view) for n, (_, view, _) in out.items()}
+    got.update(lse=lse.view(B0, H0, Sq).cpu(), d_rel=d_rel.cpu())
+    _check(got, want, kb, "padded " + _id(case), True, 0.1, rel_base)
 
 
 @pytest.mark.gpu
