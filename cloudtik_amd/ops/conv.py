@@ -123,8 +123,9 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, stride=(1, 1), padding=(0, 0), ou
         # one (mean, M2) partial per wave row block of the tile (conv.hip cv_wave_stats)
         bm = C.conv_igemm_part_rows(_CFG, co, geo[11], len(taps) // 2 * max(1, x.shape[1] // 64))
         tiles = (geo[11] + bm - 1) // bm
-        # + room for the first-level merge of the BatchNorm finalize (batchnorm.hip)
-        part = torch.empty((tiles + (tiles + 63) // 64) * 2 * co, device=x.device, dtype=torch.float32)
+        # with room for the first-level merge of the BatchNorm finalize (batchnorm_api.h): no tail
+        # up to 128 tiles, where nothing merges; conv_igemm and bn_partials_finalize use 2 tiles co
+        part = torch.empty(C.bn_given_part_floats(tiles, co), device=x.device, dtype=torch.float32)
     ok = C.conv_igemm(x, weight_rows(w).contiguous(), out, geo, taps, accumulate, part, _CFG)
     if not ok:
         raise RuntimeError(f"conv_igemm rejected x{tuple(x.shape)} w{tuple(w.shape)} s{stride} p{padding}")
@@ -697,7 +698,7 @@ def stem_fwd(x8: torch.Tensor, w: torch.Tensor, stride, padding, partials: bool 
     if partials:
         bm = C.conv_igemm_part_rows(_CFG, co, geo[11], len(_stem_taps(R, padding, pairs)) // 2)
         tiles = (geo[11] + bm - 1) // bm
-        part = torch.empty((tiles + (tiles + 63) // 64) * 2 * co, device=x8.device, dtype=torch.float32)
+        part = torch.empty(C.bn_given_part_floats(tiles, co), device=x8.device, dtype=torch.float32)
     if not C.conv_igemm(x8, stem_weight(w, pairs), out, geo, _stem_taps(R, padding, pairs), False, part, _CFG):
         raise RuntimeError(f"conv_igemm (stem) rejected x{tuple(x8.shape)} w{tuple(w.shape)}")
     if partials:

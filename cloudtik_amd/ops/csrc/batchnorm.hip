@@ -20,6 +20,7 @@
 // Channels are the contiguous dimension: a thread owns 8 channels (one 16-byte vector) and
 // walks rows, so every load is a full coalesced 16-byte-per-lane access.
 #include "common.h"
+#include "batchnorm_api.h"   // the host interface: declared once, for the bindings too
 #include <algorithm>
 #include <stdlib.h>
 
@@ -788,7 +789,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(
 }
 }  // namespace ct
 
-extern "C" int ct_bn_max_blocks() { return 2048; }
+static_assert(BN_RT * 8 == kCtBnMaxC, "a reduction block's threads own 8 channels each");
+
+extern "C" int ct_bn_max_blocks() { return kCtBnMaxBlocks; }
 
 // vectors per thread per iteration of the apply kernels (CLOUDTIK_AMD_BN_EW: 1, 2 or 4)
 static int bn_ew() {
@@ -827,25 +830,23 @@ static int bn_target_blocks() {
   return n;
 }
 
-// workspace: part = float[2 * 2048 * C]; stat = float[4 * C] (save_mean, save_invstd, a, b)
-// param_f32 (every training forward): gamma / beta are fp32 (else bf16)
-extern "C" int ct_bn_fwd_train(const void* x, const void* res, const void* gamma, const void* beta,
-                               float* run_mean, float* run_var, void* y, float* part, float* stat,
-                               int M, int C, float eps, float momentum, int relu, void* mask,
-                               int param_f32, hipStream_t stream) {
-  if (C % 8 || C / 8 > BN_RT || M <= 0) return -1;
-  BnLayout L = bn_layout(M, C, bn_target_blocks());
+// merge of n (mean, M2) partials (pm, pq: [n][C], laid out by L) into s.stat, with the
+// running-statistics update
+static void bn_finalize(const float* pm, const float* pq, int n, const BnLayout& L, const CtBnSide& s,
+                        const CtBnFwd& c, hipStream_t stream) {
+  bn_finalize_kernel<<<ceil_div(c.C, 64), 1024, 0, stream>>>(pm, pq, n, L, s.gamma, s.beta, c.param_f32, c.eps,
+                                                             c.momentum, s.run_mean, s.run_var, s.stat, s.stat + c.C,
+                                                             s.stat + 2 * c.C, s.stat + 3 * c.C);
+}
+
+// a side's own statistics pass: per-block partials into s.part (M2 rows at part + 2048 C), finalize
+static void bn_own_finalize(const CtBnSide& s, const CtBnFwd& c, hipStream_t stream) {
+  const BnLayout L = bn_layout(c.M, c.C, bn_target_blocks());
   const int nblk = bn_nblk(L);
-  if (bn_unroll() == 8) bn_stats_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
-  else bn_stats_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
-  bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)2048 * C, nblk, L,
-                                                           gamma, beta, param_f32,
-                                                           eps, momentum, run_mean, run_var, stat,
-                                                           stat + C, stat + 2 * C, stat + 3 * C);
-  const long tv = (long)M * (C / 8);
-  BN_EW_DISPATCH(bn_apply_kernel, tv, (const bf16_t*)x, (const bf16_t*)res, stat + 2 * C, stat + 3 * C,
-                 (bf16_t*)y, (uint8_t*)mask, tv, C / 8, relu);
-  return 0;
+  float* pq = s.part + (size_t)kCtBnMaxBlocks * c.C;
+  if (bn_unroll() == 8) bn_stats_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)s.x, L, s.part, pq);
+  else bn_stats_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)s.x, L, s.part, pq);
+  bn_finalize(s.part, pq, nblk, L, s, c, stream);
 }
 
 // First-level merge of per-block (mean, M2) partials: block (g, cb) merges partials
@@ -854,7 +855,7 @@ extern "C" int ct_bn_fwd_train(const void* x, const void* res, const void* gamma
 // of GROUP * rows_per_tile rows.  The conv epilogue emits one partial per 64-row wave block
 // (12544 for a ResNet-50 layer-1 conv); the single-block-per-64-channels finalize would read
 // them serially.
-constexpr int BN_MERGE_GROUP = 64;
+constexpr int BN_MERGE_GROUP = kCtBnGroup;
 // Two passes over the group's partials (they stay in cache) instead of a sequential Chan merge:
 // mean_g = sum(n_t mean_t) / sum(n_t), then M2_g = sum(M2_t + n_t (mean_t - mean_g)^2) -- no
 // division inside the loop (the dependent divisions of the sequential merge made it
@@ -927,111 +928,78 @@ static int bn_direct_tiles() {
   return n;
 }
 
-// merge (when many) + finalize of producer partials into stat = float[4C]
-static void bn_given_finalize(const float* part, int tiles, int rows_per_tile, const void* gamma, const void* beta,
-                              float* run_mean, float* run_var, float* stat, int M, int C, float eps, float momentum,
-                              int param_f32, hipStream_t stream) {
+// merge (when many) + finalize of a side's producer partials.  Up to max(2 * BN_MERGE_GROUP,
+// bn_direct_tiles()) tiles (256 by default) the finalize reads them directly; above, the merge
+// first writes groups of BN_MERGE_GROUP tiles into the tail of the partial buffer (means at
+// part + 2 tiles C, then the M2 rows) and the finalize reads the ceil(tiles / GROUP) merged ones.
+static void bn_given_finalize(const CtBnSide& s, const CtBnFwd& c, hipStream_t stream) {
+  const int M = c.M, C = c.C;
+  const float* part = s.part;
+  int tiles = s.tiles, rows_per_tile = s.rows_per_tile;
   if (tiles > std::max(2 * BN_MERGE_GROUP, bn_direct_tiles())) {
     const int groups = ceil_div(tiles, BN_MERGE_GROUP);
-    float* om = const_cast<float*>(part) + (size_t)2 * tiles * C;
+    float* om = s.part + (size_t)2 * tiles * C;
     bn_partials_merge_kernel<<<dim3(groups, ceil_div(C, 64)), 256, 0, stream>>>(
         part, part + (size_t)tiles * C, tiles, rows_per_tile, M, C, om, om + (size_t)groups * C);
     part = om;
     tiles = groups;
     rows_per_tile *= BN_MERGE_GROUP;
   }
-  BnLayout L{M, C, C / 8, 1, rows_per_tile};
-  bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)tiles * C, tiles, L,
-                                                           gamma, beta, param_f32,
-                                                           eps, momentum, run_mean, run_var, stat,
-                                                           stat + C, stat + 2 * C, stat + 3 * C);
+  const BnLayout L{M, C, C / 8, 1, rows_per_tile};
+  bn_finalize(part, part + (size_t)tiles * C, tiles, L, s, c, stream);
 }
 
-// Two BatchNorms with producer partials, y = relu(bn(x) + bn2(x2)) + bitmask (bn_apply2_kernel)
-extern "C" int ct_bn_fwd_train_given2(const void* x, const void* gamma, const void* beta, float* run_mean,
-                                      float* run_var, const float* part, int tiles, int rows_per_tile, float* stat,
-                                      const void* x2, const void* gamma2, const void* beta2, float* run_mean2,
-                                      float* run_var2, const float* part2, int tiles2, int rows_per_tile2,
-                                      float* stat2, void* y, void* mask, int M, int C, float eps, float momentum,
-                                      int param_f32, hipStream_t stream) {
-  if (C % 8 || M <= 0 || tiles <= 0 || tiles2 <= 0 || (long)tiles * rows_per_tile < M ||
-      (long)tiles2 * rows_per_tile2 < M || !mask)
-    return -1;
-  bn_given_finalize(part, tiles, rows_per_tile, gamma, beta, run_mean, run_var, stat, M, C, eps, momentum,
-                    param_f32, stream);
-  bn_given_finalize(part2, tiles2, rows_per_tile2, gamma2, beta2, run_mean2, run_var2, stat2, M, C, eps, momentum,
-                    param_f32, stream);
-  const long tv = (long)M * (C / 8);
-  bn_apply2_kernel<<<ew_grid(tv, 1), 256, 0, stream>>>((const bf16_t*)x, stat + 2 * C, stat + 3 * C,
-                                                       (const bf16_t*)x2, stat2 + 2 * C, stat2 + 3 * C, (bf16_t*)y,
-                                                       (uint8_t*)mask, tv, C / 8);
-  return hipGetLastError() == hipSuccess ? 0 : 7;
+// Refusal codes of ct_bn_fwd and ct_bn_bwd; every check runs before the first launch:
+//   -1  C % 8, M <= 0, or more than 2048 channels where a cap holds: a side that runs its own
+//       statistics pass (forward), every backward
+//   -2  backward: relu_mode outside 0..3, or mode 1 / 3 without y
+//   -3  given partials or sums: tiles < 0, or (forward) tiles * rows_per_tile < M
+//   -4  stem pool: OH, OW are not those of 3x3 / s2 / p1 over H, W; N H W != M; N * OH >= 2^31
+//   -5  a combination no caller uses.  Forward: a pair with own statistics on a side, with a
+//       residual or with the pool; the pool with a residual or a mask.  Backward: b with given
+//       sums; a pair whose a runs its own reduction; given sums with a mask (relu_mode, y) or dres
+//   -6  no descriptor, or a pair forward without its mask
+//    7  a launch failed
+static int bn_launched() { return hipGetLastError() == hipSuccess ? 0 : 7; }
+
+// a forward side's statistics source against M and C: 0, or the refusal code
+static int bn_fwd_side_refused(const CtBnSide& s, int M, int C) {
+  if (s.tiles < 0 || (s.tiles && (long)s.tiles * s.rows_per_tile < M)) return -3;
+  return (!s.tiles && C > kCtBnMaxC) ? -1 : 0;
 }
 
-extern "C" int ct_bn_fwd_train_given(const void* x, const void* res, const void* gamma, const void* beta,
-                                     float* run_mean, float* run_var, void* y, const float* part, int tiles,
-                                     int rows_per_tile, float* stat, int M, int C, float eps, float momentum,
-                                     int relu, void* mask, int param_f32, hipStream_t stream) {
-  if (C % 8 || M <= 0 || tiles <= 0 || (long)tiles * rows_per_tile < M) return -1;
-  if (tiles > std::max(2 * BN_MERGE_GROUP, bn_direct_tiles())) {
-    // merge groups of tiles first, into the tail of the partial buffer (means at
-    // part + 2 tiles C, then the M2 rows): the finalize then reads at most 2 * GROUP partials
-    const int groups = ceil_div(tiles, BN_MERGE_GROUP);
-    float* om = const_cast<float*>(part) + (size_t)2 * tiles * C;
-    bn_partials_merge_kernel<<<dim3(groups, ceil_div(C, 64)), 256, 0, stream>>>(
-        part, part + (size_t)tiles * C, tiles, rows_per_tile, M, C, om, om + (size_t)groups * C);
-    part = om;
-    tiles = groups;
-    rows_per_tile *= BN_MERGE_GROUP;
+extern "C" int ct_bn_fwd(const CtBnFwd* cp, hipStream_t stream) {
+  if (!cp) return -6;
+  const CtBnFwd& c = *cp;
+  const int M = c.M, C = c.C;
+  const bool pair = c.b.x != nullptr, pool = c.arg != nullptr;
+  if (C % 8 || M <= 0) return -1;
+  if (pair ? (!c.a.tiles || !c.b.tiles || c.res || pool) : (pool && (c.res || c.mask))) return -5;
+  if (int rc = bn_fwd_side_refused(c.a, M, C)) return rc;
+  if (pair) {
+    if (int rc = bn_fwd_side_refused(c.b, M, C)) return rc;
+    if (!c.mask) return -6;
   }
-  BnLayout L{M, C, C / 8, 1, rows_per_tile};
-  bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)tiles * C, tiles, L,
-                                                           gamma, beta, param_f32,
-                                                           eps, momentum, run_mean, run_var, stat,
-                                                           stat + C, stat + 2 * C, stat + 3 * C);
+  if (pool && (c.OH != (c.H - 1) / 2 + 1 || c.OW != (c.W - 1) / 2 + 1 || (long)c.N * c.H * c.W != M ||
+               (long)c.N * c.OH >= (1L << 31)))
+    return -4;
+
+  if (c.a.tiles) bn_given_finalize(c.a, c, stream);
+  else bn_own_finalize(c.a, c, stream);
+  if (pair) bn_given_finalize(c.b, c, stream);
+  const float *a = c.a.stat + 2 * C, *b = c.a.stat + 3 * C;
   const long tv = (long)M * (C / 8);
-  BN_EW_DISPATCH(bn_apply_kernel, tv, (const bf16_t*)x, (const bf16_t*)res, stat + 2 * C, stat + 3 * C,
-                 (bf16_t*)y, (uint8_t*)mask, tv, C / 8, relu);
-  return 0;
-}
-
-// ResNet stem: batch statistics of x, then y = maxpool3x3/s2/p1(relu(bn(x))) + byte argmax
-// (stat = float[4C] as ct_bn_fwd_train)
-extern "C" int ct_bn_fwd_train_pool(const void* x, const void* gamma, const void* beta, float* run_mean,
-                                    float* run_var, void* y, void* arg, float* part, float* stat, int N, int H, int W,
-                                    int C, int OH, int OW, float eps, float momentum, int param_f32,
-                                    hipStream_t stream) {
-  const int M = N * H * W;
-  if (C % 8 || C / 8 > BN_RT || M <= 0 || OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1) return -1;
-  BnLayout L = bn_layout(M, C, bn_target_blocks());
-  const int nblk = bn_nblk(L);
-  if (bn_unroll() == 8) bn_stats_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
-  else bn_stats_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)x, L, part, part + (size_t)2048 * C);
-  bn_finalize_kernel<<<ceil_div(C, 64), 1024, 0, stream>>>(part, part + (size_t)2048 * C, nblk, L,
-                                                           gamma, beta, param_f32,
-                                                           eps, momentum, run_mean, run_var, stat,
-                                                           stat + C, stat + 2 * C, stat + 3 * C);
-  if ((long)N * OH >= (1L << 31)) return -1;
-  bn_apply_pool_kernel<<<N * OH, 256, 0, stream>>>((const bf16_t*)x, stat + 2 * C, stat + 3 * C, (bf16_t*)y,
-                                                   (uint8_t*)arg, N, H, W, C / 8, OH, OW);
-  return 0;
-}
-
-// The same with the statistics from the stem conv's epilogue partials (conv.hip EPI 1): no
-// statistics pass over the full-resolution conv output
-extern "C" int ct_bn_fwd_train_pool_given(const void* x, const void* gamma, const void* beta, float* run_mean,
-                                          float* run_var, void* y, void* arg, const float* part, int tiles,
-                                          int rows_per_tile, float* stat, int N, int H, int W, int C, int OH, int OW,
-                                          float eps, float momentum, int param_f32, hipStream_t stream) {
-  const int M = N * H * W;
-  if (C % 8 || M <= 0 || tiles <= 0 || (long)tiles * rows_per_tile < M || OH != (H - 1) / 2 + 1 ||
-      OW != (W - 1) / 2 + 1 || (long)N * OH >= (1L << 31))
-    return -1;
-  bn_given_finalize(part, tiles, rows_per_tile, gamma, beta, run_mean, run_var, stat, M, C, eps, momentum, param_f32,
-                    stream);
-  bn_apply_pool_kernel<<<N * OH, 256, 0, stream>>>((const bf16_t*)x, stat + 2 * C, stat + 3 * C, (bf16_t*)y,
-                                                   (uint8_t*)arg, N, H, W, C / 8, OH, OW);
-  return hipGetLastError() == hipSuccess ? 0 : 7;
+  if (pair)
+    bn_apply2_kernel<<<ew_grid(tv, 1), 256, 0, stream>>>((const bf16_t*)c.a.x, a, b, (const bf16_t*)c.b.x,
+                                                         c.b.stat + 2 * C, c.b.stat + 3 * C, (bf16_t*)c.y,
+                                                         (uint8_t*)c.mask, tv, C / 8);
+  else if (pool)
+    bn_apply_pool_kernel<<<c.N * c.OH, 256, 0, stream>>>((const bf16_t*)c.a.x, a, b, (bf16_t*)c.y, (uint8_t*)c.arg,
+                                                         c.N, c.H, c.W, C / 8, c.OH, c.OW);
+  else
+    BN_EW_DISPATCH(bn_apply_kernel, tv, (const bf16_t*)c.a.x, (const bf16_t*)c.res, a, b, (bf16_t*)c.y,
+                   (uint8_t*)c.mask, tv, C / 8, c.relu);
+  return bn_launched();
 }
 
 extern "C" int ct_maxpool3s2_bwd(const void* dy, const void* arg, void* dx, int N, int H, int W, int C, int OH,
@@ -1040,7 +1008,7 @@ extern "C" int ct_maxpool3s2_bwd(const void* dy, const void* arg, void* dx, int 
   if ((long)N * H >= (1L << 31)) return -1;
   maxpool3s2_bwd_kernel<<<N * H, 256, 0, stream>>>((const bf16_t*)dy, (const uint8_t*)arg, (bf16_t*)dx, N, H, W,
                                                    C / 8, OH, OW);
-  return 0;
+  return bn_launched();
 }
 
 // partial rows (= workgroups) of ct_maxpool3s2_bwd_bn
@@ -1059,7 +1027,7 @@ extern "C" int ct_maxpool3s2_bwd_bn(const void* dy, const void* arg, const void*
   maxpool3s2_bwd_bn_kernel<<<(int)rows, 256, 0, stream>>>((const bf16_t*)dy, (const uint8_t*)arg,
                                                           (const bf16_t*)x, stat, (bf16_t*)dxm, part,
                                                           part + rows * C, N, H, W, C / 8, OH, OW);
-  return hipGetLastError() == hipSuccess ? 0 : 7;
+  return bn_launched();
 }
 
 // inference-mode forward with given affine coefficients a, b (float[C] each)
@@ -1069,51 +1037,7 @@ extern "C" int ct_bn_apply(const void* x, const void* res, const float* a, const
   const long tv = (long)M * (C / 8);
   BN_EW_DISPATCH(bn_apply_kernel, tv, (const bf16_t*)x, (const bf16_t*)res, a, b, (bf16_t*)y, (uint8_t*)nullptr, tv,
                  C / 8, relu);
-  return 0;
-}
-
-// stat = the forward's float[4C] (mean, invstd, a, b).  relu_mode: 0 none, 1 read y,
-// 2 recompute from x (no residual in the forward).  part = float[2 * 2048 * C],
-// coef = float[3 * C] scratch.
-extern "C" int ct_bn_bwd(const void* dy, const void* y, const void* x, const void* gamma, const float* stat,
-                         void* dx, void* dres, void* dgamma, void* dbeta, int param_flags, float* part,
-                         float* coef, int M, int C, int relu_mode, hipStream_t stream) {
-  if (C % 8 || C / 8 > BN_RT || M <= 0 || relu_mode < 0 || relu_mode > 3) return -1;
-  if ((relu_mode == 1 || relu_mode == 3) && !y) return -2;
-  BnLayout L = bn_layout(M, C, bn_target_blocks());
-  const int nblk = bn_nblk(L);
-  // relu_mode 3: `y` is the forward's ReLU bitmask
-  const BnMask mk{relu_mode, relu_mode == 1 ? (const bf16_t*)y : nullptr, stat + 2 * C, stat + 3 * C,
-                  relu_mode == 3 ? (const uint8_t*)y : nullptr};
-  // BN + residual add + ReLU: the reduction pass writes the masked gradient (= the residual
-  // branch's gradient, returned as dres) and the apply pass reads it back instead of dy and y:
-  // 7 instead of 8 activation-sized passes over the biggest ResNet tensors
-  bf16_t* dm = ((relu_mode == 1 || relu_mode == 3) && dres) ? (bf16_t*)dres : nullptr;
-  if (bn_unroll() == 8)
-    bn_bwd_reduce_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)dy, mk, (const bf16_t*)x, stat, stat + C, L,
-                                                        part, part + (size_t)2048 * C, dm);
-  else
-    bn_bwd_reduce_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)dy, mk, (const bf16_t*)x, stat, stat + C, L,
-                                                        part, part + (size_t)2048 * C, dm);
-  const int acc = (param_flags >> 1) & 1;   // bit 1: accumulate into dgamma / dbeta
-  if (param_flags & 1)
-    bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        part, part + (size_t)2048 * C, nblk, M, C, (const float*)gamma, stat, stat + C,
-        (float*)dgamma, (float*)dbeta, coef, coef + C, coef + 2 * C, acc);
-  else
-    bn_bwd_finalize_kernel<bf16_t><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        part, part + (size_t)2048 * C, nblk, M, C, (const bf16_t*)gamma, stat, stat + C,
-        (bf16_t*)dgamma, (bf16_t*)dbeta, coef, coef + C, coef + 2 * C, acc);
-  const long tv = (long)M * (C / 8);
-  if (dm) {
-    const BnMask none{0, nullptr, nullptr, nullptr, nullptr};
-    BN_EW_DISPATCH(bn_bwd_apply_kernel, tv, (const bf16_t*)dm, none, (const bf16_t*)x, coef, coef + C, coef + 2 * C,
-                   (bf16_t*)dx, (bf16_t*)nullptr, tv, C / 8);
-  } else {
-    BN_EW_DISPATCH(bn_bwd_apply_kernel, tv, (const bf16_t*)dy, mk, (const bf16_t*)x, coef, coef + C, coef + 2 * C,
-                   (bf16_t*)dx, (bf16_t*)dres, tv, C / 8);
-  }
-  return 0;
+  return bn_launched();
 }
 
 // first-level sum of per-tile BatchNorm-backward partials (the conv data-gradient epilogue's,
@@ -1150,93 +1074,87 @@ __global__ __launch_bounds__(256) void bn_bwd_partials_sum_kernel(const float* _
   q2[(size_t)blockIdx.x * C + c] = b;
 }
 
-// BatchNorm (+ ReLU) backward whose reduction was done by the producer of dy (conv.hip EPI 2):
-// dym = the already-masked gradient, p1 / p2 = per-tile sums [tiles][C] (p2 = p1 + p2off).
-// work = float[2 * ceil(tiles / 64) * C + 3 * C] scratch.
-// The two BatchNorm backwards of a ResNet downsample block's residual sum relu(bn(x) + bn2(x2)):
-// dym = the masked gradient (the conv epilogue's), p1 / p2 = bn's per-tile sums from that epilogue;
-// bn2's sums come from its own reduction pass over dym and x2; then ONE apply pass writes dx and
-// dx2 (bn_bwd_apply2_kernel).  param_flags as ct_bn_bwd_given (both parameter pairs alike);
-// work = float[2 * ceil(tiles / 64) * C + 3 * C], part2 = float[2 * 2048 * C], coef2 = float[3C].
-extern "C" int ct_bn_bwd_given_pair(const void* dym, const void* x, const void* gamma, const float* stat,
-                                    const float* p1, long p2off, int tiles, const void* x2, const void* gamma2,
-                                    const float* stat2, void* dx, void* dx2, void* dgamma, void* dbeta,
-                                    void* dgamma2, void* dbeta2, int param_flags, float* work, float* part2,
-                                    float* coef2, int M, int C, hipStream_t stream) {
-  if (C % 8 || C / 8 > BN_RT || C > 2048 || M <= 0 || tiles <= 0) return -1;
-  const int G = (tiles + 63) / 64;
-  float* q1 = work;
-  float* q2 = work + (size_t)G * C;
-  float* coef = q2 + (size_t)G * C;
-  int nq = G;
-  if (tiles <= bn_direct_tiles()) {
-    q1 = const_cast<float*>(p1);
-    q2 = const_cast<float*>(p1) + p2off;
-    nq = tiles;
-  } else {
-    bn_bwd_partials_sum_kernel<<<dim3(G, ceil_div(C, 256)), 256, 0, stream>>>(p1, p1 + p2off, tiles, C, q1, q2);
-  }
-  BnLayout L = bn_layout(M, C, bn_target_blocks());
+// n rows [n][C] of the two backward sums (sum dy', sum dy' xhat) that the finalize adds up
+struct BnSums { const float *q1, *q2; int n; };
+
+// a side's own reduction pass over (dy, x) into block partials in s.part; with dm it also writes
+// the masked gradient
+static BnSums bn_bwd_reduce(const void* dy, const BnMask& mk, const CtBnSide& s, const CtBnBwd& c, bf16_t* dm,
+                            hipStream_t stream) {
+  const BnLayout L = bn_layout(c.M, c.C, bn_target_blocks());
   const int nblk = bn_nblk(L);
-  const BnMask none{0, nullptr, nullptr, nullptr, nullptr};
+  float* p2 = s.part + (size_t)kCtBnMaxBlocks * c.C;
   if (bn_unroll() == 8)
-    bn_bwd_reduce_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)dym, none, (const bf16_t*)x2, stat2,
-                                                        stat2 + C, L, part2, part2 + (size_t)2048 * C, nullptr);
+    bn_bwd_reduce_kernel<8><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)dy, mk, (const bf16_t*)s.x, s.stat,
+                                                        s.stat + c.C, L, s.part, p2, dm);
   else
-    bn_bwd_reduce_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)dym, none, (const bf16_t*)x2, stat2,
-                                                        stat2 + C, L, part2, part2 + (size_t)2048 * C, nullptr);
-  const int acc = (param_flags >> 1) & 1;
-  if (param_flags & 1) {
-    bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        q1, q2, nq, M, C, (const float*)gamma, stat, stat + C, (float*)dgamma, (float*)dbeta, coef, coef + C,
-        coef + 2 * C, acc);
-    bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        part2, part2 + (size_t)2048 * C, nblk, M, C, (const float*)gamma2, stat2, stat2 + C, (float*)dgamma2,
-        (float*)dbeta2, coef2, coef2 + C, coef2 + 2 * C, acc);
-  } else {
-    bn_bwd_finalize_kernel<bf16_t><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        q1, q2, nq, M, C, (const bf16_t*)gamma, stat, stat + C, (bf16_t*)dgamma, (bf16_t*)dbeta, coef, coef + C,
-        coef + 2 * C, acc);
-    bn_bwd_finalize_kernel<bf16_t><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        part2, part2 + (size_t)2048 * C, nblk, M, C, (const bf16_t*)gamma2, stat2, stat2 + C, (bf16_t*)dgamma2,
-        (bf16_t*)dbeta2, coef2, coef2 + C, coef2 + 2 * C, acc);
-  }
-  const long tv = (long)M * (C / 8);
-  bn_bwd_apply2_kernel<<<ew_grid(tv, 1), 256, 0, stream>>>((const bf16_t*)dym, (const bf16_t*)x, coef, coef + C,
-                                                           coef + 2 * C, (const bf16_t*)x2, coef2, coef2 + C,
-                                                           coef2 + 2 * C, (bf16_t*)dx, (bf16_t*)dx2, tv, C / 8);
-  return hipGetLastError() == hipSuccess ? 0 : 7;
+    bn_bwd_reduce_kernel<4><<<nblk, BN_RT, 0, stream>>>((const bf16_t*)dy, mk, (const bf16_t*)s.x, s.stat,
+                                                        s.stat + c.C, L, s.part, p2, dm);
+  return {s.part, p2, nblk};
 }
 
-extern "C" int ct_bn_bwd_given(const void* dym, const void* x, const void* gamma, const float* stat, void* dx,
-                               void* dgamma, void* dbeta, int param_flags, const float* p1, long p2off, int tiles,
-                               float* work, int M, int C, hipStream_t stream) {
-  if (C % 8 || C > 2048 || M <= 0 || tiles <= 0) return -1;
-  const int G = (tiles + 63) / 64;
-  float* q1 = work;
-  float* q2 = work + (size_t)G * C;
-  float* coef = q2 + (size_t)G * C;
-  int nq = G;
-  if (tiles <= bn_direct_tiles()) {            // the finalize sums the tile partials itself
-    q1 = const_cast<float*>(p1);
-    q2 = const_cast<float*>(p1) + p2off;
-    nq = tiles;
-  } else {
-    bn_bwd_partials_sum_kernel<<<dim3(G, ceil_div(C, 256)), 256, 0, stream>>>(p1, p1 + p2off, tiles, C, q1, q2);
-  }
-  const int acc = (param_flags >> 1) & 1;
-  if (param_flags & 1)
+// a side's given per-tile sums: read directly by the finalize up to bn_direct_tiles() tiles, else
+// summed first in groups of 64 tiles into the head of s.work
+static BnSums bn_given_sums(const CtBnSide& s, int C, hipStream_t stream) {
+  if (s.tiles <= bn_direct_tiles()) return {s.p1, s.p1 + s.p2off, s.tiles};
+  const int G = (int)ct_bn_groups(s.tiles);
+  float *q1 = s.work, *q2 = s.work + (size_t)G * C;
+  bn_bwd_partials_sum_kernel<<<dim3(G, ceil_div(C, 256)), 256, 0, stream>>>(s.p1, s.p1 + s.p2off, s.tiles, C, q1, q2);
+  return {q1, q2, G};
+}
+
+// dgamma, dbeta (accumulated with param_flags bit 1) and coef = (ca, c1, c0) of a side from its sums
+static void bn_bwd_finalize(const BnSums& q, const CtBnSide& s, float* coef, const CtBnBwd& c, hipStream_t stream) {
+  const int M = c.M, C = c.C, acc = (c.param_flags >> 1) & 1;
+  if (c.param_flags & 1)
     bn_bwd_finalize_kernel<float><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        q1, q2, nq, M, C, (const float*)gamma, stat, stat + C, (float*)dgamma, (float*)dbeta, coef, coef + C,
-        coef + 2 * C, acc);
+        q.q1, q.q2, q.n, M, C, (const float*)s.gamma, s.stat, s.stat + C, (float*)s.dgamma, (float*)s.dbeta, coef,
+        coef + C, coef + 2 * C, acc);
   else
     bn_bwd_finalize_kernel<bf16_t><<<ceil_div(C, 64), 1024, 0, stream>>>(
-        q1, q2, nq, M, C, (const bf16_t*)gamma, stat, stat + C, (bf16_t*)dgamma, (bf16_t*)dbeta, coef, coef + C,
-        coef + 2 * C, acc);
-  if (dx == nullptr) return hipGetLastError() == hipSuccess ? 0 : 7;   // coefficients only (work + 2 G C)
-  const long tv = (long)M * (C / 8);
-  const BnMask none{0, nullptr, nullptr, nullptr, nullptr};
-  BN_EW_DISPATCH(bn_bwd_apply_kernel, tv, (const bf16_t*)dym, none, (const bf16_t*)x, coef, coef + C, coef + 2 * C,
-                 (bf16_t*)dx, (bf16_t*)nullptr, tv, C / 8);
-  return hipGetLastError() == hipSuccess ? 0 : 7;
+        q.q1, q.q2, q.n, M, C, (const bf16_t*)s.gamma, s.stat, s.stat + C, (bf16_t*)s.dgamma, (bf16_t*)s.dbeta, coef,
+        coef + C, coef + 2 * C, acc);
 }
+
+// BatchNorm (+ ReLU) backward: the two sums of each side, its finalize, then one apply pass.
+//   a's own reduction: the mask comes from relu_mode; with a residual in the forward (modes 1, 3)
+//     and dres, the reduction pass writes the masked gradient (= the residual branch's gradient,
+//     returned as dres) and the apply pass reads it back instead of dy and y: 7 instead of 8
+//     activation-sized passes over the biggest ResNet tensors.
+//   a's given sums: the producer of dy reduced (conv.hip EPI 2, ct_maxpool3s2_bwd_bn) and masked
+//     it.  Without a.dx only dgamma, dbeta and coef (the tail of a.work) are computed.
+//   + b: the BatchNorms of a ResNet downsample block's relu(bn(x) + bn2(x2)); b reduces dy and
+//     b.x itself, then ONE apply pass writes a.dx and b.dx (bn_bwd_apply2_kernel).
+extern "C" int ct_bn_bwd(const CtBnBwd* cp, hipStream_t stream) {
+  if (!cp) return -6;
+  const CtBnBwd& c = *cp;
+  const int M = c.M, C = c.C, mode = c.relu_mode;
+  const bool given = c.a.tiles != 0, pair = c.b.x != nullptr;
+  if (C % 8 || C > kCtBnMaxC || M <= 0) return -1;
+  if (c.a.tiles < 0 || c.b.tiles < 0) return -3;
+  if (c.b.tiles || (pair && !given) || (given && (mode || c.y || c.dres))) return -5;
+  if (mode < 0 || mode > 3 || ((mode == 1 || mode == 3) && !c.y)) return -2;
+  if (!given && !c.a.dx) return -6;
+
+  // relu_mode 3: `y` is the forward's ReLU bitmask
+  const BnMask none{0, nullptr, nullptr, nullptr, nullptr};
+  const BnMask mk{mode, mode == 1 ? (const bf16_t*)c.y : nullptr, c.a.stat + 2 * C, c.a.stat + 3 * C,
+                  mode == 3 ? (const uint8_t*)c.y : nullptr};
+  bf16_t* dm = ((mode == 1 || mode == 3) && c.dres) ? (bf16_t*)c.dres : nullptr;
+  float *coef = given ? c.a.work + 2 * ct_bn_groups(c.a.tiles) * C : c.a.coef, *coef2 = c.b.coef;
+  const BnSums qa = given ? bn_given_sums(c.a, C, stream) : bn_bwd_reduce(c.dy, mk, c.a, c, dm, stream);
+  const BnSums qb = pair ? bn_bwd_reduce(c.dy, none, c.b, c, nullptr, stream) : BnSums{};
+  bn_bwd_finalize(qa, c.a, coef, c, stream);
+  if (pair) bn_bwd_finalize(qb, c.b, coef2, c, stream);
+  const long tv = (long)M * (C / 8);
+  if (pair)
+    bn_bwd_apply2_kernel<<<ew_grid(tv, 1), 256, 0, stream>>>(
+        (const bf16_t*)c.dy, (const bf16_t*)c.a.x, coef, coef + C, coef + 2 * C, (const bf16_t*)c.b.x, coef2,
+        coef2 + C, coef2 + 2 * C, (bf16_t*)c.a.dx, (bf16_t*)c.b.dx, tv, C / 8);
+  else if (c.a.dx)   // a gradient that is masked already (given, or dm) needs neither mask nor dres
+    BN_EW_DISPATCH(bn_bwd_apply_kernel, tv, dm ? dm : (const bf16_t*)c.dy, (given || dm) ? none : mk,
+                   (const bf16_t*)c.a.x, coef, coef + C, coef + 2 * C, (bf16_t*)c.a.dx,
+                   dm ? nullptr : (bf16_t*)c.dres, tv, C / 8);
+  return bn_launched();
+}
+

@@ -44,29 +44,6 @@ int ct_sumsq(const void*, int, long, float*, float*, hipStream_t);
 int ct_clip_coef(const float*, float*, float, float, hipStream_t);
 int ct_xent_fwd(const void*, void*, int, int, const int64_t*, float*, float*, const float*, int, int,
                 float, hipStream_t);
-int ct_bn_fwd_train(const void*, const void*, const void*, const void*, float*, float*, void*, float*,
-                    float*, int, int, float, float, int, void*, int, hipStream_t);
-int ct_bn_apply(const void*, const void*, const float*, const float*, void*, int, int, int, hipStream_t);
-int ct_bn_fwd_train_given(const void*, const void*, const void*, const void*, float*, float*, void*, const float*, int,
-                          int, float*, int, int, float, float, int, void*, int, hipStream_t);
-int ct_bn_fwd_train_pool_given(const void*, const void*, const void*, float*, float*, void*, void*, const float*, int, int,
-                               float*, int, int, int, int, int, int, float, float, int, hipStream_t);
-int ct_bn_fwd_train_pool(const void*, const void*, const void*, float*, float*, void*, void*, float*, float*, int, int,
-                         int, int, int, int, float, float, int, hipStream_t);
-int ct_maxpool3s2_bwd(const void*, const void*, void*, int, int, int, int, int, int, hipStream_t);
-int ct_bn_fwd_train_given2(const void*, const void*, const void*, float*, float*, const float*, int, int, float*,
-                           const void*, const void*, const void*, float*, float*, const float*, int, int, float*,
-                           void*, void*, int, int, float, float, int, hipStream_t);
-int ct_maxpool3s2_bwd_bn(const void*, const void*, const void*, const float*, void*, float*, int, int, int, int, int,
-                         int, hipStream_t);
-long ct_maxpool3s2_bwd_bn_rows(int, int);
-int ct_bn_bwd_given_pair(const void*, const void*, const void*, const float*, const float*, long, int, const void*,
-                         const void*, const float*, void*, void*, void*, void*, void*, void*, int, float*, float*,
-                         float*, int, int, hipStream_t);
-int ct_bn_bwd_given(const void*, const void*, const void*, const float*, void*, void*, void*, int, const float*, long,
-                    int, float*, int, int, hipStream_t);
-int ct_bn_bwd(const void*, const void*, const void*, const void*, const float*, void*, void*, void*, void*, int,
-              float*, float*, int, int, int, hipStream_t);
 }
 
 #define CHECK_CUDA(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")
@@ -563,385 +540,6 @@ void attn_bwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at
   TORCH_CHECK(rc == 0, "attn_bwd_relbias failed rc=", rc);
 }
 
-// ---------------------------------------------------------------- batchnorm (NHWC)
-static void check_nhwc(const at::Tensor& x, const char* name) {
-  CHECK_CUDA(x); CHECK_BF16(x);
-  TORCH_CHECK(x.dim() == 4 ? x.is_contiguous(at::MemoryFormat::ChannelsLast) : x.is_contiguous(),
-              name, " must be channels_last (4-D) or contiguous [M, C]");
-}
-static int64_t nhwc_rows(const at::Tensor& x) { return x.numel() / x.size(1); }
-
-// optional ReLU bitmask output of the training forwards: uint8, one byte per 8 channels
-static void* mask_ptr(const c10::optional<at::Tensor>& mask, const at::Tensor& x) {
-  if (!mask.has_value() || !mask->defined()) return nullptr;
-  TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
-              mask->numel() * 8 == x.numel(), "ReLU mask: uint8 [numel / 8]");
-  return mask->data_ptr();
-}
-
-// gamma / beta (and the gamma of a backward) arrive in bf16 or in fp32 -- BatchNorm parameters kept
-// in fp32 beside bf16 activations -- and the kernels read them in that dtype: 1 when fp32
-static int bn_param_f32(const at::Tensor& gamma, const char* name) {
-  TORCH_CHECK(gamma.is_cuda() && (gamma.scalar_type() == at::kBFloat16 || gamma.scalar_type() == at::kFloat), name,
-              ": BatchNorm parameters must be bf16 or fp32 CUDA tensors");
-  return gamma.scalar_type() == at::kFloat ? 1 : 0;
-}
-static int bn_param_f32(const at::Tensor& gamma, const at::Tensor& beta, const char* name) {
-  TORCH_CHECK(beta.is_cuda() && beta.scalar_type() == gamma.scalar_type(), name, ": gamma and beta must share a dtype");
-  return bn_param_f32(gamma, name);
-}
-
-// returns (y, stat) with stat = float[4C]: save_mean, save_invstd, a, b (y = x * a + b ...);
-// mask_out (optional, uint8 [numel / 8]) receives the ReLU bitmask (bit j of byte v: y > 0)
-std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor gamma,
-                                     at::Tensor beta, at::Tensor run_mean, at::Tensor run_var,
-                                     double eps, double momentum, bool relu,
-                                     c10::optional<at::Tensor> mask_out) {
-  check_nhwc(x, "x");
-  const int C = x.size(1);
-  const long M = nhwc_rows(x);
-  TORCH_CHECK(C <= 2048, "bn_fwd_train: C <= 2048");
-  if (res.has_value() && res->defined()) { check_nhwc(*res, "residual"); TORCH_CHECK(res->sizes() == x.sizes()); }
-  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && run_mean.numel() == C && run_var.numel() == C);
-  CHECK_F32(run_mean); CHECK_F32(run_var);
-  const int pf32 = bn_param_f32(gamma, beta, "bn_fwd_train");
-  auto y = at::empty_like(x);
-  auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
-  auto part = at::empty({2 * 2048 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_fwd_train(x.data_ptr(), optr(res), gamma.data_ptr(), beta.data_ptr(),
-                           run_mean.data_ptr<float>(), run_var.data_ptr<float>(), y.data_ptr(),
-                           part.data_ptr<float>(), stat.data_ptr<float>(), (int)M, C, (float)eps,
-                           (float)momentum, relu ? 1 : 0, mask_ptr(mask_out, x), pf32, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_fwd_train: unsupported C=", C);
-  return {y, stat};
-}
-
-// bn_fwd_train with the statistics already reduced per tile by x's producer (conv epilogue):
-// part = means [tiles][C] then M2 [tiles][C], tiles = ceil(M / rows_per_tile)
-std::vector<at::Tensor> bn_fwd_train_given(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor gamma,
-                                           at::Tensor beta, at::Tensor run_mean, at::Tensor run_var, at::Tensor part,
-                                           int64_t rows_per_tile, double eps, double momentum, bool relu,
-                                           c10::optional<at::Tensor> mask_out) {
-  check_nhwc(x, "x");
-  const int C = x.size(1);
-  const long M = nhwc_rows(x);
-  if (res.has_value() && res->defined()) { check_nhwc(*res, "residual"); TORCH_CHECK(res->sizes() == x.sizes()); }
-  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && run_mean.numel() == C && run_var.numel() == C);
-  CHECK_F32(run_mean); CHECK_F32(run_var); CHECK_IN(part); CHECK_F32(part);
-  const long tiles = (M + rows_per_tile - 1) / rows_per_tile;
-  // the tail holds the first-level merge (ct_bn_fwd_train_given) when there are many tiles
-  TORCH_CHECK(part.numel() >= 2 * (tiles + (tiles > 128 ? (tiles + 63) / 64 : 0)) * C,
-              "bn_fwd_train_given: part buffer");
-  const int pf32 = bn_param_f32(gamma, beta, "bn_fwd_train_given");
-  auto y = at::empty_like(x);
-  auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_fwd_train_given(x.data_ptr(), optr(res), gamma.data_ptr(), beta.data_ptr(),
-                                 run_mean.data_ptr<float>(), run_var.data_ptr<float>(), y.data_ptr(),
-                                 part.data_ptr<float>(), (int)tiles, (int)rows_per_tile, stat.data_ptr<float>(),
-                                 (int)M, C, (float)eps, (float)momentum, relu ? 1 : 0, mask_ptr(mask_out, x),
-                                 pf32, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_fwd_train_given: unsupported C=", C);
-  return {y, stat};
-}
-
-// y = relu(bn(x) + bn2(x2)) with both BatchNorms' statistics from their producers' partials (the
-// ResNet downsample block: bn3(conv3) + down_bn(down)): returns (y, mask bytes, stat, stat2)
-std::vector<at::Tensor> bn_fwd_train_given2(at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor run_mean,
-                                            at::Tensor run_var, at::Tensor part, int64_t rows_per_tile,
-                                            at::Tensor x2, at::Tensor gamma2, at::Tensor beta2,
-                                            at::Tensor run_mean2, at::Tensor run_var2, at::Tensor part2,
-                                            int64_t rows_per_tile2, double eps, double momentum) {
-  check_nhwc(x, "x");
-  check_nhwc(x2, "x2");
-  TORCH_CHECK(x2.sizes() == x.sizes() && x2.strides() == x.strides(), "bn_fwd_train_given2: x2 layout");
-  const int C = x.size(1);
-  const long M = nhwc_rows(x);
-  for (const at::Tensor* t : {&gamma, &beta, &run_mean, &run_var, &gamma2, &beta2, &run_mean2, &run_var2})
-    TORCH_CHECK(t->numel() == C, "bn_fwd_train_given2: per-channel tensors");
-  CHECK_F32(run_mean); CHECK_F32(run_var); CHECK_F32(run_mean2); CHECK_F32(run_var2);
-  CHECK_IN(part); CHECK_F32(part); CHECK_IN(part2); CHECK_F32(part2);
-  const long tiles = (M + rows_per_tile - 1) / rows_per_tile, tiles2 = (M + rows_per_tile2 - 1) / rows_per_tile2;
-  TORCH_CHECK(part.numel() >= 2 * (tiles + (tiles > 128 ? (tiles + 63) / 64 : 0)) * C &&
-              part2.numel() >= 2 * (tiles2 + (tiles2 > 128 ? (tiles2 + 63) / 64 : 0)) * C,
-              "bn_fwd_train_given2: part buffers");
-  const int pf32 = bn_param_f32(gamma, beta, "bn_fwd_train_given2");
-  TORCH_CHECK(bn_param_f32(gamma2, beta2, "bn_fwd_train_given2") == pf32, "bn_fwd_train_given2: parameter dtypes");
-  auto y = at::empty_like(x);
-  auto mask = at::empty({x.numel() / 8}, x.options().dtype(at::kByte));
-  auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
-  auto stat2 = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_fwd_train_given2(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), run_mean.data_ptr<float>(),
-                                  run_var.data_ptr<float>(), part.data_ptr<float>(), (int)tiles, (int)rows_per_tile,
-                                  stat.data_ptr<float>(), x2.data_ptr(), gamma2.data_ptr(), beta2.data_ptr(),
-                                  run_mean2.data_ptr<float>(), run_var2.data_ptr<float>(), part2.data_ptr<float>(),
-                                  (int)tiles2, (int)rows_per_tile2, stat2.data_ptr<float>(), y.data_ptr(),
-                                  mask.data_ptr(), (int)M, C, (float)eps, (float)momentum, pf32, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_fwd_train_given2: unsupported C=", C);
-  return {y, mask, stat, stat2};
-}
-
-// backward of bn_fwd_train_given2 with the masked gradient and bn's partials from the consuming
-// conv's epilogue: [dx, dx2, dgamma, dbeta, dgamma2, dbeta2] (accumulated into the *_acc targets,
-// all four or none, when given)
-std::vector<at::Tensor> bn_bwd_given_pair(at::Tensor dym, at::Tensor x, at::Tensor gamma, at::Tensor stat,
-                                          at::Tensor part, int64_t tiles, int64_t rows, at::Tensor x2,
-                                          at::Tensor gamma2, at::Tensor stat2,
-                                          c10::optional<at::Tensor> dgamma_acc, c10::optional<at::Tensor> dbeta_acc,
-                                          c10::optional<at::Tensor> dgamma2_acc,
-                                          c10::optional<at::Tensor> dbeta2_acc) {
-  check_nhwc(x, "x");
-  check_nhwc(x2, "x2");
-  check_nhwc(dym, "dym");
-  const int C = x.size(1);
-  const long M = nhwc_rows(x);
-  TORCH_CHECK(dym.sizes() == x.sizes() && dym.strides() == x.strides() && x2.sizes() == x.sizes() &&
-              x2.strides() == x.strides(), "bn_bwd_given_pair: layouts");
-  TORCH_CHECK(C <= 2048 && stat.numel() == 4 * (long)C && stat2.numel() == 4 * (long)C, "bn_bwd_given_pair: stat");
-  CHECK_F32(stat); CHECK_F32(stat2); CHECK_F32(part);
-  TORCH_CHECK(tiles > 0 && tiles <= rows && part.numel() >= 2 * rows * C, "bn_bwd_given_pair: part buffer");
-  TORCH_CHECK(gamma2.scalar_type() == gamma.scalar_type() && gamma.numel() == C && gamma2.numel() == C,
-              "bn_bwd_given_pair: parameter dtypes");
-  const int pf32 = bn_param_f32(gamma, "bn_bwd_given_pair");
-  const bool acc = dgamma_acc.has_value() && dgamma_acc->defined();
-  for (const auto* t : {&dbeta_acc, &dgamma2_acc, &dbeta2_acc})
-    TORCH_CHECK((t->has_value() && (*t)->defined()) == acc, "bn_bwd_given_pair: accumulate targets: all or none");
-  if (acc) {
-    for (const auto* t : {&dgamma_acc, &dbeta_acc, &dgamma2_acc, &dbeta2_acc})
-      TORCH_CHECK((*t)->is_contiguous() && (*t)->numel() == C && (*t)->scalar_type() == gamma.scalar_type(),
-                  "bn_bwd_given_pair: bad accumulate target");
-  }
-  auto dx = at::empty_like(x), dx2 = at::empty_like(x2);
-  auto dg = acc ? *dgamma_acc : at::empty_like(gamma), db = acc ? *dbeta_acc : at::empty_like(gamma);
-  auto dg2 = acc ? *dgamma2_acc : at::empty_like(gamma2), db2 = acc ? *dbeta2_acc : at::empty_like(gamma2);
-  const long G = (tiles + 63) / 64;
-  auto work = at::empty({2 * G * C + 3 * (long)C}, x.options().dtype(at::kFloat));
-  auto part2 = at::empty({2 * 2048 * (long)C}, x.options().dtype(at::kFloat));
-  auto coef2 = at::empty({3 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_bwd_given_pair(dym.data_ptr(), x.data_ptr(), gamma.data_ptr(), stat.data_ptr<float>(),
-                                part.data_ptr<float>(), rows * C, (int)tiles, x2.data_ptr(), gamma2.data_ptr(),
-                                stat2.data_ptr<float>(), dx.data_ptr(), dx2.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                dg2.data_ptr(), db2.data_ptr(),
-                                pf32 | (acc ? 2 : 0), work.data_ptr<float>(),
-                                part2.data_ptr<float>(), coef2.data_ptr<float>(), (int)M, C, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_bwd_given_pair: unsupported C=", C);
-  return {dx, dx2, dg, db, dg2, db2};
-}
-
-// ResNet stem: returns (y_pool [N, C, OH, OW] channels_last, argmax bytes [N, OH, OW, C] uint8, stat)
-std::vector<at::Tensor> bn_fwd_train_pool(at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor run_mean,
-                                          at::Tensor run_var, double eps, double momentum) {
-  check_nhwc(x, "x");
-  TORCH_CHECK(x.dim() == 4, "bn_fwd_train_pool: 4-D NHWC input");
-  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  TORCH_CHECK(C % 8 == 0 && C <= 2048, "bn_fwd_train_pool: C % 8 == 0, C <= 2048");
-  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && run_mean.numel() == C && run_var.numel() == C);
-  CHECK_F32(run_mean); CHECK_F32(run_var);
-  auto y = at::empty({N, C, OH, OW}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  auto arg = at::empty({N, OH, OW, C}, x.options().dtype(at::kByte));
-  auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
-  auto part = at::empty({2 * 2048 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_fwd_train_pool(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), run_mean.data_ptr<float>(),
-                                run_var.data_ptr<float>(), y.data_ptr(), arg.data_ptr(), part.data_ptr<float>(),
-                                stat.data_ptr<float>(), N, H, W, C, OH, OW, (float)eps, (float)momentum,
-                                bn_param_f32(gamma, beta, "bn_fwd_train_pool"), cur_stream());
-  TORCH_CHECK(rc == 0, "bn_fwd_train_pool: unsupported shape");
-  return {y, arg, stat};
-}
-
-// bn_fwd_train_pool with the statistics from the conv epilogue's per-tile partials (part, rows
-// per tile: conv_fwd(..., partials=True)); returns (y_pool, argmax bytes, stat)
-std::vector<at::Tensor> bn_fwd_train_pool_given(at::Tensor x, at::Tensor gamma, at::Tensor beta,
-                                                at::Tensor run_mean, at::Tensor run_var, at::Tensor part,
-                                                int64_t rows_per_tile, double eps, double momentum) {
-  check_nhwc(x, "x");
-  TORCH_CHECK(x.dim() == 4, "bn_fwd_train_pool_given: 4-D NHWC input");
-  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const long M = (long)N * H * W;
-  TORCH_CHECK(C % 8 == 0 && C <= 2048, "bn_fwd_train_pool_given: C % 8 == 0, C <= 2048");
-  TORCH_CHECK(gamma.numel() == C && beta.numel() == C && run_mean.numel() == C && run_var.numel() == C);
-  CHECK_F32(run_mean); CHECK_F32(run_var); CHECK_IN(part); CHECK_F32(part);
-  TORCH_CHECK(rows_per_tile > 0, "bn_fwd_train_pool_given: rows per tile");
-  const long tiles = (M + rows_per_tile - 1) / rows_per_tile;
-  TORCH_CHECK(part.numel() >= 2 * (tiles + (tiles > 128 ? (tiles + 63) / 64 : 0)) * C,
-              "bn_fwd_train_pool_given: part buffer");
-  auto y = at::empty({N, C, OH, OW}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  auto arg = at::empty({N, OH, OW, C}, x.options().dtype(at::kByte));
-  auto stat = at::empty({4 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_fwd_train_pool_given(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), run_mean.data_ptr<float>(),
-                                      run_var.data_ptr<float>(), y.data_ptr(), arg.data_ptr(), part.data_ptr<float>(),
-                                      (int)tiles, (int)rows_per_tile, stat.data_ptr<float>(), N, H, W, C, OH, OW,
-                                      (float)eps, (float)momentum, bn_param_f32(gamma, beta, "bn_fwd_train_pool_given"),
-                                      cur_stream());
-  TORCH_CHECK(rc == 0, "bn_fwd_train_pool_given: unsupported shape");
-  return {y, arg, stat};
-}
-
-// gradient of maxpool3x3/s2/p1 from the byte argmax: dx [N, C, H, W] channels_last
-at::Tensor maxpool3s2_bwd(at::Tensor dy, at::Tensor arg, int64_t H, int64_t W) {
-  at::Tensor dyc = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  check_nhwc(dyc, "dy");
-  const int N = dyc.size(0), C = dyc.size(1), OH = dyc.size(2), OW = dyc.size(3);
-  TORCH_CHECK(arg.scalar_type() == at::kByte && arg.is_contiguous() && arg.numel() == dyc.numel(),
-              "maxpool3s2_bwd: argmax bytes");
-  TORCH_CHECK(OH == (H - 1) / 2 + 1 && OW == (W - 1) / 2 + 1 && C % 8 == 0, "maxpool3s2_bwd: shape");
-  auto dx = at::empty({N, C, (long)H, (long)W}, dyc.options().memory_format(at::MemoryFormat::ChannelsLast));
-  int rc = ct_maxpool3s2_bwd(dyc.data_ptr(), arg.data_ptr(), dx.data_ptr(), N, (int)H, (int)W, C, OH, OW,
-                             cur_stream());
-  TORCH_CHECK(rc == 0, "maxpool3s2_bwd: unsupported shape");
-  return dx;
-}
-
-// stem backward: the max-pool gradient gather + the BatchNorm's ReLU mask and backward sums in one
-// pass; returns the masked gradient (at x's shape) and fills part (float[2 * rows * C]: p1 rows
-// then p2 rows, rows = maxpool3s2_bwd_bn_rows(N, H) tiles) for bn_bwd_given
-at::Tensor maxpool3s2_bwd_bn(at::Tensor dy, at::Tensor arg, at::Tensor x, at::Tensor stat, at::Tensor part) {
-  at::Tensor dyc = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  check_nhwc(dyc, "dy");
-  check_nhwc(x, "x");
-  CHECK_F32(stat);
-  CHECK_F32(part);
-  const int N = dyc.size(0), C = dyc.size(1), OH = dyc.size(2), OW = dyc.size(3);
-  const int H = x.size(2), W = x.size(3);
-  TORCH_CHECK(x.size(0) == N && x.size(1) == C && stat.numel() == 4 * (long)C, "maxpool3s2_bwd_bn: shapes");
-  TORCH_CHECK(arg.scalar_type() == at::kByte && arg.is_contiguous() && arg.numel() == dyc.numel(),
-              "maxpool3s2_bwd_bn: argmax bytes");
-  TORCH_CHECK(part.is_contiguous() && part.numel() >= 2L * ct_maxpool3s2_bwd_bn_rows(N, H) * C,
-              "maxpool3s2_bwd_bn: part buffer");
-  auto dxm = at::empty_like(x);
-  int rc = ct_maxpool3s2_bwd_bn(dyc.data_ptr(), arg.data_ptr(), x.data_ptr(), stat.data_ptr<float>(), dxm.data_ptr(),
-                                part.data_ptr<float>(), N, H, W, C, OH, OW, cur_stream());
-  TORCH_CHECK(rc == 0, "maxpool3s2_bwd_bn: unsupported shape");
-  return dxm;
-}
-
-at::Tensor bn_apply(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor a, at::Tensor b, bool relu) {
-  check_nhwc(x, "x");
-  const int C = x.size(1);
-  CHECK_F32(a); CHECK_F32(b); TORCH_CHECK(a.numel() == C && b.numel() == C);
-  auto y = at::empty_like(x);
-  int rc = ct_bn_apply(x.data_ptr(), optr(res), a.data_ptr<float>(), b.data_ptr<float>(), y.data_ptr(),
-                       (int)nhwc_rows(x), C, relu ? 1 : 0, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_apply: unsupported C");
-  return y;
-}
-
-// returns (dx, dres, dgamma, dbeta).  relu_mode: 0 no ReLU, 1 mask from y (forward had a
-// residual), 2 mask recomputed from x and the forward's (a, b) -- y may be undefined then,
-// 3 y is the forward's ReLU bitmask (uint8 [numel / 8]).
-std::vector<at::Tensor> bn_bwd(at::Tensor dy, c10::optional<at::Tensor> y, at::Tensor x, at::Tensor gamma,
-                               at::Tensor stat, int64_t relu_mode, bool need_dres,
-                               c10::optional<at::Tensor> dgamma_acc, c10::optional<at::Tensor> dbeta_acc) {
-  check_nhwc(x, "x");
-  at::Tensor dyc = dy.dim() == 4 ? dy.contiguous(at::MemoryFormat::ChannelsLast) : dy.contiguous();
-  check_nhwc(dyc, "dy");
-  const int C = x.size(1);
-  const long M = nhwc_rows(x);
-  TORCH_CHECK(C <= 2048 && stat.numel() == 4 * (long)C, "bn_bwd: stat must be float[4C], C <= 2048");
-  CHECK_F32(stat);
-  TORCH_CHECK(relu_mode >= 0 && relu_mode <= 3, "bn_bwd: relu_mode 0/1/2/3");
-  TORCH_CHECK(gamma.numel() == C, "bn_bwd: gamma must have C elements");
-  const int pf32 = bn_param_f32(gamma, "bn_bwd");
-  if (relu_mode == 1) {
-    TORCH_CHECK(y.has_value() && y->defined(), "bn_bwd: relu_mode 1 needs y");
-    check_nhwc(*y, "y");
-    TORCH_CHECK(y->sizes() == x.sizes(), "bn_bwd: y shape");
-  }
-  if (relu_mode == 3) {
-    TORCH_CHECK(y.has_value() && y->defined(), "bn_bwd: relu_mode 3 needs the mask");
-    mask_ptr(y, x);
-  }
-  TORCH_CHECK(dyc.sizes() == x.sizes(), "bn_bwd: dy shape");
-  auto dx = at::empty_like(x);
-  at::Tensor dres = need_dres ? at::empty_like(x) : at::Tensor();
-  // optional accumulate targets (flat gradient buffer views): both or neither
-  const bool acc = dgamma_acc.has_value() && dgamma_acc->defined();
-  if (acc) {
-    TORCH_CHECK(dbeta_acc.has_value() && dbeta_acc->defined(), "bn_bwd: dgamma_acc needs dbeta_acc");
-    TORCH_CHECK(dgamma_acc->is_contiguous() && dbeta_acc->is_contiguous() && dgamma_acc->numel() == C &&
-                dbeta_acc->numel() == C && dgamma_acc->scalar_type() == gamma.scalar_type() &&
-                dbeta_acc->scalar_type() == gamma.scalar_type(), "bn_bwd: bad accumulate targets");
-  }
-  auto dgamma = acc ? *dgamma_acc : at::empty_like(gamma), dbeta = acc ? *dbeta_acc : at::empty_like(gamma);
-  auto coef = at::empty({3 * (long)C}, x.options().dtype(at::kFloat));
-  auto part = at::empty({2 * 2048 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_bwd(dyc.data_ptr(), (relu_mode == 1 || relu_mode == 3) ? y->data_ptr() : nullptr, x.data_ptr(),
-                     gamma.data_ptr(),
-                     stat.data_ptr<float>(), dx.data_ptr(), need_dres ? dres.data_ptr() : nullptr,
-                     dgamma.data_ptr(), dbeta.data_ptr(),
-                     pf32 | (acc ? 2 : 0), part.data_ptr<float>(),
-                     coef.data_ptr<float>(), (int)M, C, (int)relu_mode, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_bwd: unsupported C=", C);
-  return {dx, dres, dgamma, dbeta};
-}
-
-// BatchNorm (+ ReLU) backward from the reduction done by the conv that produced dy
-// (conv_igemm_bn): dym = the masked gradient, part = float[2 * rows * C] per-tile sums (first
-// `tiles` rows of each half).  Returns (dx, dgamma, dbeta).
-std::vector<at::Tensor> bn_bwd_given(at::Tensor dym, at::Tensor x, at::Tensor gamma, at::Tensor stat, at::Tensor part,
-                                     int64_t tiles, int64_t rows, c10::optional<at::Tensor> dgamma_acc,
-                                     c10::optional<at::Tensor> dbeta_acc) {
-  check_nhwc(x, "x");
-  check_nhwc(dym, "dym");
-  const int C = x.size(1);
-  const long M = nhwc_rows(x);
-  TORCH_CHECK(dym.sizes() == x.sizes() && dym.strides() == x.strides(), "bn_bwd_given: dym / x layout");
-  TORCH_CHECK(C <= 2048 && stat.numel() == 4 * (long)C, "bn_bwd_given: stat must be float[4C], C <= 2048");
-  CHECK_F32(stat);
-  CHECK_F32(part);
-  TORCH_CHECK(tiles > 0 && tiles <= rows && part.numel() >= 2 * rows * C, "bn_bwd_given: part buffer");
-  TORCH_CHECK(gamma.numel() == C, "bn_bwd_given: gamma must have C elements");
-  const int pf32 = bn_param_f32(gamma, "bn_bwd_given");
-  const bool acc = dgamma_acc.has_value() && dgamma_acc->defined();
-  if (acc) {
-    TORCH_CHECK(dbeta_acc.has_value() && dbeta_acc->defined(), "bn_bwd_given: dgamma_acc needs dbeta_acc");
-    TORCH_CHECK(dgamma_acc->is_contiguous() && dbeta_acc->is_contiguous() && dgamma_acc->numel() == C &&
-                dbeta_acc->numel() == C && dgamma_acc->scalar_type() == gamma.scalar_type() &&
-                dbeta_acc->scalar_type() == gamma.scalar_type(), "bn_bwd_given: bad accumulate targets");
-  }
-  auto dx = at::empty_like(x);
-  auto dgamma = acc ? *dgamma_acc : at::empty_like(gamma), dbeta = acc ? *dbeta_acc : at::empty_like(gamma);
-  const long G = (tiles + 63) / 64;
-  auto work = at::empty({2 * G * C + 3 * (long)C}, x.options().dtype(at::kFloat));
-  int rc = ct_bn_bwd_given(dym.data_ptr(), x.data_ptr(), gamma.data_ptr(), stat.data_ptr<float>(), dx.data_ptr(),
-                           dgamma.data_ptr(), dbeta.data_ptr(),
-                           pf32 | (acc ? 2 : 0), part.data_ptr<float>(),
-                           rows * C, (int)tiles, work.data_ptr<float>(), (int)M, C, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_bwd_given: unsupported C=", C);
-  return {dx, dgamma, dbeta};
-}
-
-// The BatchNorm backward's per-channel results WITHOUT the apply pass: (dgamma, dbeta, coef) from
-// the producer's per-tile sums, coef = float[3C] = (ca, c1, c0) with dx = ca dym + c1 x + c0.  For
-// a BatchNorm whose input gradient only feeds a weight gradient (the ResNet stem: dW = ca G1 +
-// c1 G2 + c0 G0 over the conv's im2col columns, ops/functional.py _StemBlockFn).
-std::vector<at::Tensor> bn_bwd_coefs_given(int64_t M, at::Tensor gamma, at::Tensor stat, at::Tensor part,
-                                           int64_t tiles, int64_t rows, c10::optional<at::Tensor> dgamma_acc,
-                                           c10::optional<at::Tensor> dbeta_acc) {
-  const int C = (int)gamma.numel();
-  TORCH_CHECK(gamma.is_cuda() && C % 8 == 0 && C <= 2048 && stat.numel() == 4 * (long)C, "bn_bwd_coefs_given: stat");
-  CHECK_F32(stat);
-  CHECK_F32(part);
-  TORCH_CHECK(M > 0 && tiles > 0 && tiles <= rows && part.numel() >= 2 * rows * C, "bn_bwd_coefs_given: part buffer");
-  const int pf32 = bn_param_f32(gamma, "bn_bwd_coefs_given");
-  const bool acc = dgamma_acc.has_value() && dgamma_acc->defined();
-  if (acc) {
-    TORCH_CHECK(dbeta_acc.has_value() && dbeta_acc->defined() && dgamma_acc->is_contiguous() &&
-                dbeta_acc->is_contiguous() && dgamma_acc->numel() == C && dbeta_acc->numel() == C &&
-                dgamma_acc->scalar_type() == gamma.scalar_type() && dbeta_acc->scalar_type() == gamma.scalar_type(),
-                "bn_bwd_coefs_given: bad accumulate targets");
-  }
-  auto dgamma = acc ? *dgamma_acc : at::empty_like(gamma), dbeta = acc ? *dbeta_acc : at::empty_like(gamma);
-  const long G = (tiles + 63) / 64;
-  auto work = at::empty({2 * G * C + 3 * (long)C}, gamma.options().dtype(at::kFloat));
-  int rc = ct_bn_bwd_given(nullptr, nullptr, gamma.data_ptr(), stat.data_ptr<float>(), nullptr, dgamma.data_ptr(),
-                           dbeta.data_ptr(), pf32 | (acc ? 2 : 0),
-                           part.data_ptr<float>(), rows * C, (int)tiles, work.data_ptr<float>(), (int)M, C, cur_stream());
-  TORCH_CHECK(rc == 0, "bn_bwd_coefs_given: unsupported C=", C);
-  return {dgamma, dbeta, work.narrow(0, 2 * G * C, 3 * (long)C)};
-}
-
 void register_ext(pybind11::module& m);   // bindings_ext.cpp
 void register_graph(pybind11::module& m); // bindings_graph.cpp
 void register_deform(pybind11::module& m); // bindings_deform.cpp
@@ -953,6 +551,7 @@ void register_beam(pybind11::module& m);   // bindings_beam.cpp
 void register_sampling(pybind11::module& m); // bindings_sampling.cpp
 void register_constrain(pybind11::module& m); // bindings_constrain.cpp
 void register_quant_skinny(pybind11::module& m); // bindings_quant_skinny.cpp
+void register_bn(pybind11::module& m);     // bindings_bn.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "cloudtik_amd CDNA4 (gfx950) op library";
@@ -967,10 +566,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_sampling(m);
   register_constrain(m);
   register_quant_skinny(m);
-  m.def("maxpool3s2_bwd_bn", &maxpool3s2_bwd_bn);
-  m.def("bn_fwd_train_given2", &bn_fwd_train_given2);
-  m.def("bn_bwd_given_pair", &bn_bwd_given_pair);
-  m.def("maxpool3s2_bwd_bn_rows", [](int64_t N, int64_t H) { return (int64_t)ct_maxpool3s2_bwd_bn_rows((int)N, (int)H); });
+  register_bn(m);
   m.def("layernorm_fwd", &layernorm_fwd, pybind11::arg("x"), pybind11::arg("bias"), pybind11::arg("res"),
         pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("eps"), pybind11::arg("rms"),
         pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("offset"), pybind11::arg("keep_sum") = true);
@@ -996,20 +592,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sumsq_into", &sumsq_into);
   m.def("clip_coef", &clip_coef);
   m.def("xent_fwd", &xent_fwd);
-  m.def("bn_fwd_train", &bn_fwd_train, pybind11::arg("x"), pybind11::arg("res"), pybind11::arg("gamma"),
-        pybind11::arg("beta"), pybind11::arg("run_mean"), pybind11::arg("run_var"), pybind11::arg("eps"),
-        pybind11::arg("momentum"), pybind11::arg("relu"), pybind11::arg("mask_out") = pybind11::none());
-  m.def("bn_apply", &bn_apply);
-  m.def("bn_fwd_train_given", &bn_fwd_train_given, pybind11::arg("x"), pybind11::arg("res"), pybind11::arg("gamma"),
-        pybind11::arg("beta"), pybind11::arg("run_mean"), pybind11::arg("run_var"), pybind11::arg("part"),
-        pybind11::arg("rows_per_tile"), pybind11::arg("eps"), pybind11::arg("momentum"), pybind11::arg("relu"),
-        pybind11::arg("mask_out") = pybind11::none());
-  m.def("bn_fwd_train_pool", &bn_fwd_train_pool);
-  m.def("bn_fwd_train_pool_given", &bn_fwd_train_pool_given);
-  m.def("maxpool3s2_bwd", &maxpool3s2_bwd);
-  m.def("bn_bwd", &bn_bwd);
-  m.def("bn_bwd_given", &bn_bwd_given);
-  m.def("bn_bwd_coefs_given", &bn_bwd_coefs_given);
   m.def("attn_fwd_relbias", &attn_fwd_relbias);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);

@@ -216,6 +216,22 @@ def cross_entropy_fused(x, W, b, labels, V=None, ignore_index=-100, label_smooth
 _BN_RELU_BITMASK = os.environ.get("CLOUDTIK_AMD_BN_RELU_BITMASK", "1") == "1"
 
 
+def _bn_flat_grads(wp, bp, gamma):
+    """Whether the backward may accumulate dgamma / dbeta straight into ``wp.grad`` / ``bp.grad``:
+    both are contiguous views of the flat gradient buffer in gamma's dtype."""
+    return all(p is not None and p.grad is not None and getattr(p, "_ct_flat_grad", False)
+               and p.grad.is_contiguous() and p.grad.dtype == gamma.dtype for p in (wp, bp))
+
+
+def _grads_ready(*params):
+    """Tell the owners of parameters whose gradients were accumulated in place (no AccumulateGrad
+    hook fires for them)."""
+    for p in params:
+        cb = getattr(p, "_ct_grad_ready", None)
+        if cb is not None:
+            cb(p)
+
+
 class _BNActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, run_mean, run_var, relu, momentum, eps):
@@ -249,8 +265,7 @@ class _BNActFn(torch.autograd.Function):
         x, y, gamma, stat = ctx.saved_tensors
         mode, has_res = ctx.cfg
         wp, bp = ctx.params
-        flat = all(p is not None and p.grad is not None and getattr(p, "_ct_flat_grad", False)
-                   and p.grad.is_contiguous() and p.grad.dtype == gamma.dtype for p in (wp, bp))
+        flat = _bn_flat_grads(wp, bp, gamma)
         given = ctx.bn_link.take(dy) if ctx.bn_link is not None else None
         if given is not None and dy.is_contiguous(memory_format=torch.channels_last):
             # dy arrives ReLU-masked with its reduction done by the conv's dgrad epilogue
@@ -259,10 +274,7 @@ class _BNActFn(torch.autograd.Function):
             if flat:
                 dx, _, _ = _C().bn_bwd_given(dy, x, gamma, stat, part, tiles, rows, wp.grad, bp.grad)
                 flush_deferred_wgrads()         # the producing conv's weight gradient (ops/conv.py)
-                for p in (wp, bp):
-                    cb = getattr(p, "_ct_grad_ready", None)
-                    if cb is not None:
-                        cb(p)
+                _grads_ready(wp, bp)
                 # with a residual add the masked dy IS the residual branch's gradient
                 return dx, None, None, (dy if has_res else None), None, None, None, None, None
             dx, dg, db = _C().bn_bwd_given(dy, x, gamma, stat, part, tiles, rows, None, None)
@@ -271,10 +283,7 @@ class _BNActFn(torch.autograd.Function):
         if flat:
             # accumulate straight into the flat gradient buffer (no AccumulateGrad kernels)
             dx, dres, _, _ = _C().bn_bwd(dy, y, x, gamma, stat, mode, has_res, wp.grad, bp.grad)
-            for p in (wp, bp):
-                cb = getattr(p, "_ct_grad_ready", None)
-                if cb is not None:
-                    cb(p)
+            _grads_ready(wp, bp)
             return dx, None, None, (dres if has_res else None), None, None, None, None, None
         dx, dres, dg, db = _C().bn_bwd(dy, y, x, gamma, stat, mode, has_res, None, None)
         return dx, dg, db, (dres if has_res else None), None, None, None, None, None
@@ -309,18 +318,7 @@ class _BNAddBNActFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, mask, gamma, stat, x2, gamma2, stat2 = ctx.saved_tensors
         wp, bp, wp2, bp2 = ctx.params
-
-        def flat_ok(w, b, g):
-            return all(p is not None and p.grad is not None and getattr(p, "_ct_flat_grad", False)
-                       and p.grad.is_contiguous() and p.grad.dtype == g.dtype for p in (w, b))
-
-        def ready(*ps):
-            for p in ps:
-                cb = getattr(p, "_ct_grad_ready", None)
-                if cb is not None:
-                    cb(p)
-
-        f1, f2 = flat_ok(wp, bp, gamma), flat_ok(wp2, bp2, gamma2)
+        f1, f2 = _bn_flat_grads(wp, bp, gamma), _bn_flat_grads(wp2, bp2, gamma2)
         given = ctx.bn_link.take(dy)
         dg = db = dg2 = db2 = None
         if (_BN_PAIR_BWD and given is not None and dy.is_contiguous(memory_format=torch.channels_last)
@@ -333,7 +331,7 @@ class _BNAddBNActFn(torch.autograd.Function):
             from cloudtik_amd.ops.conv import flush_deferred_wgrads
             flush_deferred_wgrads()
             if f1:
-                ready(wp, bp, wp2, bp2)
+                _grads_ready(wp, bp, wp2, bp2)
                 return dx, None, None, None, None, dx2, None, None, None, None, None, None
             return dx, dg, db, None, None, dx2, dg2, db2, None, None, None, None
         if given is not None and dy.is_contiguous(memory_format=torch.channels_last):
@@ -348,13 +346,13 @@ class _BNAddBNActFn(torch.autograd.Function):
                                           wp.grad if f1 else None, bp.grad if f1 else None)
         if f1:
             dg = db = None
-            ready(wp, bp)
+            _grads_ready(wp, bp)
         # the downsample BatchNorm (no ReLU) sees the masked gradient, as the residual input did
         dx2, _, dg2, db2 = _C().bn_bwd(dym, None, x2, gamma2, stat2, 0, False,
                                        wp2.grad if f2 else None, bp2.grad if f2 else None)
         if f2:
             dg2 = db2 = None
-            ready(wp2, bp2)
+            _grads_ready(wp2, bp2)
         return dx, dg, db, None, None, dx2, dg2, db2, None, None, None, None
 
 
@@ -377,14 +375,10 @@ def batch_norm_add_bn_act(x, weight, bias, running_mean, running_var, x2, weight
 def _bn_param_grads(wp, bp, gamma, x, stat, dy, y, mode, has_res):
     """BN backward shared by the BN(+ReLU)(+pool) autograd functions: accumulates the affine
     gradients straight into the flat gradient buffer when the parameters live there."""
-    flat = all(p is not None and p.grad is not None and getattr(p, "_ct_flat_grad", False)
-               and p.grad.is_contiguous() and p.grad.dtype == gamma.dtype for p in (wp, bp))
+    flat = _bn_flat_grads(wp, bp, gamma)
     if flat:
         dx, dres, _, _ = _C().bn_bwd(dy, y, x, gamma, stat, mode, has_res, wp.grad, bp.grad)
-        for p in (wp, bp):
-            cb = getattr(p, "_ct_grad_ready", None)
-            if cb is not None:
-                cb(p)
+        _grads_ready(wp, bp)
         return dx, dres, None, None
     return tuple(_C().bn_bwd(dy, y, x, gamma, stat, mode, has_res, None, None))
 
@@ -425,14 +419,10 @@ class _BNReLUPoolFn(torch.autograd.Function):
             rows = _C().maxpool3s2_bwd_bn_rows(x.shape[0], x.shape[2])
             part = torch.empty(2 * rows * x.shape[1], device=x.device, dtype=torch.float32)
             dym = _C().maxpool3s2_bwd_bn(dyp, arg, x, stat, part)
-            flat = all(p is not None and p.grad is not None and getattr(p, "_ct_flat_grad", False)
-                       and p.grad.is_contiguous() and p.grad.dtype == gamma.dtype for p in (wp, bp))
+            flat = _bn_flat_grads(wp, bp, gamma)
             if flat:
                 dx, _, _ = _C().bn_bwd_given(dym, x, gamma, stat, part, rows, rows, wp.grad, bp.grad)
-                for p in (wp, bp):
-                    cb = getattr(p, "_ct_grad_ready", None)
-                    if cb is not None:
-                        cb(p)
+                _grads_ready(wp, bp)
                 return dx, None, None, None, None, None, None
             dx, dg, db = _C().bn_bwd_given(dym, x, gamma, stat, part, rows, rows, None, None)
             return dx, dg, db, None, None, None, None
@@ -506,15 +496,11 @@ class _StemBlockFn(torch.autograd.Function):
         part = torch.empty(2 * rows * y.shape[1], device=y.device, dtype=torch.float32)
         dym = C.maxpool3s2_bwd_bn(dyp.contiguous(memory_format=torch.channels_last), arg, y, stat, part)
         M = y.numel() // y.shape[1]
-        flat = all(p is not None and p.grad is not None and getattr(p, "_ct_flat_grad", False)
-                   and p.grad.is_contiguous() and p.grad.dtype == gamma.dtype for p in (wp, bp))
+        flat = _bn_flat_grads(wp, bp, gamma)
         dg, db, coef = C.bn_bwd_coefs_given(M, gamma, stat, part, rows, rows, wp.grad if flat else None,
                                             bp.grad if flat else None)
         if flat:
-            for p in (wp, bp):
-                cb = getattr(p, "_ct_grad_ready", None)
-                if cb is not None:
-                    cb(p)
+            _grads_ready(wp, bp)
             dg = db = None
         dw = None
         if ctx.g is not None:
@@ -532,9 +518,7 @@ class _StemBlockFn(torch.autograd.Function):
             target = _flat_target(ctx.wp)
             if target is not None:                    # straight into the flat gradient buffer
                 target.add_(dw)
-                cb = getattr(ctx.wp, "_ct_grad_ready", None)
-                if cb is not None:
-                    cb(ctx.wp)
+                _grads_ready(ctx.wp)
                 dw = None
         return None, dw, dg, db, None, None, None, None, None, None
 

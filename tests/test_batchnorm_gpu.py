@@ -1094,6 +1094,41 @@ def test_bindings_reject_other_parameter_dtypes(cuda):
     assert _worst(_chan(_mc(yp), _pool(want["y"], SHAPE4[7]))) <= BOUND["y_pool"]
 
 
+@pytest.mark.gpu
+def test_refused_call_touches_nothing(cuda):
+    """A refused call has launched nothing: the running statistics and the accumulate targets a
+    refused ``bn_fwd_train`` (C 12, 2056), ``bn_fwd_train_pool`` (C 12), ``bn_bwd`` (C 12) or
+    ``bn_bwd_given`` (tiles > rows) was handed still hold their pattern.  N 1, H 2, W 3: M = 6."""
+    K = ops.require_native()
+    N, H, W = 1, 2, 3
+    M = N * H * W
+
+    def pattern(C, dtype=F32):
+        return (0.25 * (1 + torch.arange(C) % 13)).to(dtype).to(cuda)
+
+    def refused(C, call):
+        g = _gen("untouched", C)
+        x = torch.randn(M, C, generator=g).bfloat16().to(cuda)
+        gamma, beta = torch.ones(C, dtype=BF16, device=cuda), torch.zeros(C, dtype=BF16, device=cuda)
+        bufs = [pattern(C), pattern(C) + 1]
+        with pytest.raises(RuntimeError):
+            call(x, gamma, beta, *bufs)
+        torch.cuda.synchronize()
+        assert torch.equal(bufs[0], pattern(C)) and torch.equal(bufs[1], pattern(C) + 1), "C %d" % C
+
+    for C in (12, 2056):
+        refused(C, lambda x, g, b, rm, rv: K.bn_fwd_train(x, None, g, b, rm, rv, EPS, 0.1, True, None))
+    refused(12, lambda x, g, b, rm, rv: K.bn_fwd_train_pool(_as4(x, (N, H, W)), g, b, rm, rv, EPS, 0.1))
+
+    def stat(C):
+        return torch.ones(4 * C, device=cuda)
+
+    refused(12, lambda x, g, b, dg, db: K.bn_bwd(x, None, x, g.float(), stat(12), 2, False, dg, db))
+    tiles, rows = 3, 2
+    refused(16, lambda x, g, b, dg, db: K.bn_bwd_given(x, x, g.float(), stat(16), torch.zeros(2 * rows * 16, device=cuda),
+                                                       tiles, rows, dg, db))
+
+
 # ------------------------------------------------------------------ the knobs read once per process
 _KNOBS = ("CLOUDTIK_AMD_BN_EW", "CLOUDTIK_AMD_BN_UNROLL", "CLOUDTIK_AMD_BN_BLOCKS", "CLOUDTIK_AMD_BN_DIRECT_TILES")
 _VARIANTS = [{"CLOUDTIK_AMD_BN_EW": "2"}, {"CLOUDTIK_AMD_BN_EW": "4"}, {"CLOUDTIK_AMD_BN_UNROLL": "8"},
