@@ -10,7 +10,11 @@ events; every figure is the median round with the min and max next to it (the ru
 ``torch.cuda.max_memory_allocated`` is reset before and read after a round of each route.  The
 loss of both routes on the same batch (dropout off for that one comparison) is printed too.
 
-    python bench/t5_train_probe.py [rounds] [iters] [--trace]
+    python bench/t5_train_probe.py [rounds] [iters] [--trace] [--xl]
+
+``--xl``: the d_kv = 128 topology instead of T5-base: a SLICE of t5-3b, its width (d_model 1024,
+32 heads x 128, d_ff 16384) with 2 + 2 layers instead of 24 + 24, so every layer has the 3B
+model's shapes and the step fits a short run; the figures are per-slice, not a 3B step time.
 
 ``--trace``: no timing; three steps of the kernel route at each shape, for a separate
 ``rocprofv3 --kernel-trace --stats -- python bench/t5_train_probe.py --trace`` run.
@@ -74,6 +78,7 @@ def main():
     rounds = int(args[0]) if args else 5
     iters = int(args[1]) if len(args) > 1 else 10
     trace = "--trace" in sys.argv
+    xl = "--xl" in sys.argv
     from cloudtik_amd import ops
     from cloudtik_amd.models.t5 import T5Config, T5ForConditionalGeneration
     ops.require_native()
@@ -83,7 +88,13 @@ def main():
                       "trace": trace}), flush=True)
     torch.manual_seed(0)
     ops.manual_seed(0)
-    model = T5ForConditionalGeneration(T5Config.base(dropout_rate=0.1), device=dev).train()
+    if xl:
+        import dataclasses
+        cfg = dataclasses.replace(T5Config.xl(dropout_rate=0.1), num_layers=2, num_decoder_layers=2)
+        label = "t5-3b slice, 2 + 2 layers"
+    else:
+        cfg, label = T5Config.base(dropout_rate=0.1), "t5-base"
+    model = T5ForConditionalGeneration(cfg, device=dev).train()
     routes = {"kernels": "1", "sdpa": "0"}
     for B, S, T in SHAPES:
         batch = _batch(B, S, T, model.cfg.vocab_size, dev)
@@ -116,7 +127,7 @@ def main():
                 runs[name].append(_ms(model, batch, iters))
                 peak[name] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
         res = {k: _summary(v) for k, v in runs.items()}
-        print(json.dumps({"model": "t5-base (random init, dropout 0.1)", "batch": B, "source": S, "target": T,
+        print(json.dumps({"model": label + " (random init, dropout 0.1)", "d_kv": cfg.d_kv, "batch": B, "source": S, "target": T,
                           "step_ms": res, "peak_mib": peak, "loss_no_dropout": losses,
                           "speedup_median": round(res["sdpa"]["median"] / res["kernels"]["median"], 3)}), flush=True)
     os.environ.pop(SWITCH, None)

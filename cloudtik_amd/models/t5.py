@@ -140,7 +140,7 @@ def relative_position_bucket(rel: torch.Tensor, bidirectional: bool, num_buckets
 
 
 def train_attention_kernels() -> bool:
-    """Whether d_kv-64 attention takes the HIP kernels in grad mode and under dropout (default);
+    """Whether d_kv 64 / 128 attention takes the HIP kernels in grad mode and under dropout (default);
     ``CLOUDTIK_AMD_T5_TRAIN_ATTN=0`` keeps those calls on ``F.scaled_dot_product_attention`` with
     a materialised bias, the earlier routing (the A/B switch of bench/t5_train_probe.py)."""
     return os.environ.get("CLOUDTIK_AMD_T5_TRAIN_ATTN", "1") != "0"
@@ -213,22 +213,27 @@ class T5Attention(nn.Module):
         Sk = k.shape[1]
         grad = torch.is_grad_enabled() and self.training
         kernel_ok = q.is_cuda and q.dtype == torch.bfloat16 and self.dk in (64, 128)
-        if self.dk == 128 and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-            kernel_ok = False                     # the head-dim-128 kernel is forward only: SDPA below
         # causal masking in the kernel is top-left aligned: exact for prefill (offset 0) and for
         # single-token decode steps (every cached key is visible)
         causal = self.causal and S > 1
-        # d_kv 64 trains on the kernels: self-attention with the bias gradient and dropout
-        # (ops.attention_relbias), cross-attention with dropout (ops.attention).
+        # d_kv 64 and 128 train on the kernels: self-attention with the bias gradient and dropout
+        # (ops.attention_relbias), cross-attention with dropout (ops.attention at d_kv 64,
+        # ops.attention_relbias(rel_bias=None) at 128, where ops.attention has no training kernels).
         # CLOUDTIK_AMD_T5_TRAIN_ATTN=0 sends grad-mode and dropout calls back to SDPA below.
-        train_kernels = self.dk == 64 and train_attention_kernels()
+        train_kernels = train_attention_kernels()
+        needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+        if self.dk == 128 and not train_kernels and needs_grad:
+            kernel_ok = False
         p = self.cfg.dropout_rate if (self.training and train_kernels) else 0.0
         if rel is not None and kernel_ok and (train_kernels or not grad) and (offset == 0 or not causal):
             relvec, rel_base = rel
             o = ops.attention_relbias(q, k, v, relvec, rel_base, key_bias, scale=1.0, causal=causal, p=p)
         elif rel is None and kernel_ok and (train_kernels or not (self.training and self.cfg.dropout_rate)):
-            o = ops.attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), key_bias=key_bias, p=p,
-                              scale=1.0, causal=causal).transpose(1, 2)          # T5 folds the scale into init
+            if self.dk == 128 and (needs_grad or p > 0):
+                o = ops.attention_relbias(q, k, v, None, 0, key_bias, scale=1.0, causal=causal, p=p)
+            else:
+                o = ops.attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), key_bias=key_bias, p=p,
+                                  scale=1.0, causal=causal).transpose(1, 2)      # T5 folds the scale into init
         else:
             bias = None
             if rel is not None:

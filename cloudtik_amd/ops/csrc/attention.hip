@@ -1,6 +1,7 @@
-// Fused multi-head attention on CDNA4 MFMA, bf16 I/O: forward + backward at head_dim 64, and an
-// inference forward at head_dim 128 (attn_fwd_d128_kernel: T5-3B / T5-11B, d_kv = 128; forward
-// only, no dropout; its header comment states its LDS plan).
+// Fused multi-head attention on CDNA4 MFMA, bf16 I/O: forward + backward at head_dim 64 and at
+// head_dim 128 (T5-3B / T5-11B, d_kv = 128: attn_fwd_d128_kernel, whose header comment states its
+// LDS plan, for inference and the p = 0 training forward; attn_fwd_d128_drop_kernel and
+// attn_bwd_d128_kernel in attention_d128_train.h for training).
 //
 // Hot op of the reference's BERT-large pretraining: HF BertSelfAttention, 16 heads x 64,
 // S = 128 (phase-1 shards) / 512, padding mask + attention-prob dropout 0.1
@@ -40,7 +41,9 @@
 // Head dim 128 (attn_fwd_d128_kernel<CAUSAL, REL>): the forward above with 8 k-steps for S^T and
 // four O^T blocks; a K/V tile is two 64-column halves in the d64 LDS image; K/V by
 // global_load_lds into a two-deep ring; the relative-bias stage is dynamic LDS sized to the
-// vector, so two workgroups share a CU.
+// vector, so two workgroups share a CU.  Its training kernels (the forward with dropout, and the
+// backward: the d64 backward widened to 128 columns, one workgroup per CU) are in
+// attention_d128_train.h.
 #include "common.h"
 #include "attention_api.h"
 #include <cstdlib>
@@ -860,6 +863,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d64_rel_kernel(AttnBwdArgs a)
 #include "attention_bwd_d64_body.h"
 }
 
+#include "attention_d128_train.h"
+
 // d_rel[h][i] (fp32, strided) = the sum over (batch, key block), in that fixed order, of the
 // workspace windows that hold offset i; every entry is written, an offset in no window as 0.
 __global__ void attn_drel_reduce_kernel(const float* __restrict__ ws, float* __restrict__ drel, long d_sh, long d_si,
@@ -876,13 +881,13 @@ __global__ void attn_drel_reduce_kernel(const float* __restrict__ ws, float* __r
   drel[h * d_sh + i * d_si] = acc;
 }
 
-// dq (bf16, strided) = dq_acc (fp32 [B*H, Sq, 64])
+// dq (bf16, strided) = dq_acc (fp32 [B*H, Sq, D]), D = 1 << dshift
 __global__ void attn_dq_convert_kernel(const float* __restrict__ acc, bf16_t* __restrict__ dq,
-                                       long sb, long ss, long sh, int B, int H, int Sq) {
+                                       long sb, long ss, long sh, int B, int H, int Sq, int dshift) {
   const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (t >= (long)B * H * Sq * 64) return;
-  const int d = t & 63;
-  const long row = t >> 6;
+  if (t >= ((long)B * H * Sq) << dshift) return;
+  const int d = t & ((1 << dshift) - 1);
+  const long row = t >> dshift;
   const int q = row % Sq;
   const int bh = row / Sq;
   const int b = bh / H, h = bh % H;
@@ -944,9 +949,13 @@ static int attn_persistent_grid(long nitems, int per_cu) {
 // attn_bwd_d64_kernel); the kernel keeps two windows (8 W bytes) of dynamic LDS next to its
 // 66,048 static bytes, and two workgroups per CU (what __launch_bounds__(256, 2) and the
 // register budget are for) leave 160 KiB / 2 - 66,048 = 15,872 bytes: W <= 1984, Sq <= 1856.
+// The D = 128 backward has one workgroup per CU: 160 KiB - kBwd128Static (115,200) = 48,640 bytes,
+// W <= 6080, which every call with relb_len <= kCtAttnRelBiasMax meets (W <= Sq + 158 there).
 constexpr int kBwdRelMaxWindow = (160 * 1024 / 2 - 66048) / 8;
+constexpr int kBwd128RelMaxWindow = (160 * 1024 - kBwd128Static) / 8;
 extern "C" int ct_attn_bwd_relbias_window(int Sq) { return 32 * ((Sq + 31) / 32) + 127; }
 extern "C" int ct_attn_bwd_relbias_max_window() { return kBwdRelMaxWindow; }
+extern "C" int ct_attn_bwd_relbias_max_window_d(int D) { return D == 128 ? kBwd128RelMaxWindow : kBwdRelMaxWindow; }
 
 // the kernels index rows inside one (batch, head) slice with 32-bit offsets; a row is D elements
 static bool fits32(const CtAttnView& t, long rows, int D) { return rows * t.ss + D < (1L << 31); }
@@ -955,22 +964,23 @@ static bool aligned16(const CtAttnView& t) { return !(((uintptr_t)t.p & 15) || t
 
 // The refusals of ct_attn_fwd / ct_attn_bwd, in the order the codes are listed; every one comes
 // before the first memset or launch, so a refused call has written nothing.
-//    -1  a non-positive size, a D other than 64 (128: forward without dropout), or a missing
-//        pointer: lse for the d64 relative-bias forward, d_rel / drel_ws for the relative-bias
-//        backward; relb with relb_len <= 0
+//    -1  a non-positive size, a D other than 64 or 128, or a missing pointer: lse for the d64
+//        relative-bias forward, d_rel / drel_ws for the relative-bias backward; relb with
+//        relb_len <= 0
 //    -2  p > 0 with odd Sk (the dropout stream is drawn per element pair)
 //    -4  relb_len > kCtAttnRelBiasMax
 //   -10  backward: relb does not cover every (key - query) offset
 //    -5  a tensor's rows do not fit 32-bit offsets
 //    -7  o (forward) or dk / dv (backward) not 16-byte aligned
-//    -9  relative-bias backward: the windows would not leave room for two workgroups per CU
-//    -3  backward: Sk > 128 without dq_acc
+//    -9  relative-bias backward: the windows do not fit next to the kernel's static LDS (D 64: two
+//        workgroups per CU; D 128: one)
+//    -3  backward: Sk > 128 without dq_acc (float[B H Sq D])
 //    -6  forward, CLOUDTIK_AMD_ATTN_FWD_PIPE route only: item count (refused by ct_attn_fwd itself)
 //    -8  a launch or the memset failed (not a refusal: the stream may hold part of the call)
 static int attn_refusal(const CtAttnCall& c, bool bwd) {
   const bool rel = c.relb != nullptr;
   if (c.B <= 0 || c.H <= 0 || c.Sq <= 0 || c.Sk <= 0 || (rel && c.relb_len <= 0)) return -1;
-  if (c.D != 64 && (c.D != 128 || bwd || c.p_drop > 0.f)) return -1;
+  if (c.D != 64 && c.D != 128) return -1;
   if (rel && (bwd ? !c.d_rel || !c.drel_ws : c.D == 64 && !c.lse)) return -1;
   if (c.p_drop > 0.f && (c.Sk % 2)) return -2;
   if (rel && c.relb_len > kCtAttnRelBiasMax) return -4;
@@ -979,7 +989,7 @@ static int attn_refusal(const CtAttnCall& c, bool bwd) {
     return -5;
   if (bwd && (!fits32(c.dO, c.Sq, c.D) || !fits32(c.dq, c.Sq, c.D))) return -5;
   if (bwd ? !aligned16(c.dk) || !aligned16(c.dv) : !aligned16(c.o)) return -7;
-  if (bwd && rel && ct_attn_bwd_relbias_window(c.Sq) > kBwdRelMaxWindow) return -9;
+  if (bwd && rel && ct_attn_bwd_relbias_window(c.Sq) > ct_attn_bwd_relbias_max_window_d(c.D)) return -9;
   if (bwd && c.Sk > 128 && !c.dq_acc) return -3;
   return 0;
 }
@@ -1019,8 +1029,8 @@ template <int N> using int_c = std::integral_constant<int, N>;
 static int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : -8; }
 
 // Forward: writes o and lse (lse may be null without relb).  Dispatch:
-//   D 128           attn_fwd_d128_kernel<CAUSAL, REL> (inference: no dropout), the relative-bias stage in
-//                   dynamic LDS
+//   D 128           attn_fwd_d128_kernel<CAUSAL, REL> at p = 0 (inference, and training when given lse),
+//                   attn_fwd_d128_drop_kernel<CAUSAL, REL> at p > 0; the relative-bias stage in dynamic LDS
 //   D 64, relb      attn_fwd_d64_kernel<DROP, CAUSAL, REL = true>, two workgroups per CU (T5: inference at
 //                   p = 0, training with the dropout stream of the plain forward)
 //   D 64            attn_fwd_d64_kernel<DROP, CAUSAL, false, WPE, GL>, or attn_fwd_pipe_kernel, by the knobs
@@ -1034,7 +1044,8 @@ extern "C" int ct_attn_fwd(const CtAttnCall* call, hipStream_t stream) {
   if (c.D == 128) {
     const size_t dyn = rel ? (size_t)c.relb_len * sizeof(float) : 0;
     with_bools(causal, rel, [&](auto CA, auto RE) {
-      attn_fwd_d128_kernel<CA.value, RE.value><<<grid, 256, dyn, stream>>>(a);
+      if (drop) attn_fwd_d128_drop_kernel<CA.value, RE.value><<<grid, 256, dyn, stream>>>(a);
+      else attn_fwd_d128_kernel<CA.value, RE.value><<<grid, 256, dyn, stream>>>(a);
     });
     return launch_rc();
   }
@@ -1081,13 +1092,15 @@ extern "C" int ct_attn_fwd(const CtAttnCall* call, hipStream_t stream) {
   return launch_rc();
 }
 
-// Backward (D 64): writes dq, dk, dv and, with relb, every entry of d_rel.  Dispatch:
+// Backward: writes dq, dk, dv and, with relb, every entry of d_rel.  Dispatch at D 64:
 //   no relb   attn_bwd_d64_kernel<DROP, CAUSAL, MULTI, GL>: Sk > 128 -> MULTI (dQ summed in dq_acc, zeroed
 //             here, then attn_dq_convert_kernel); otherwise one key block, by LDS DMA (GL) when Sq <= 128
 //             and CLOUDTIK_AMD_ATTN_BWD_GL is not 0
 //   relb      attn_bwd_d64_rel_kernel<DROP, CAUSAL, MULTI>: the register-staged single-block form for
 //             every Sq when Sk <= 128 (REL has no LDS-DMA form); two windows of dynamic LDS; then
 //             attn_drel_reduce_kernel sums the windows in drel_ws into d_rel
+// At D 128 every call runs attn_bwd_d128_kernel<DROP, CAUSAL, MULTI, REL> (register-staged, one workgroup
+// per CU), followed by the same convert (Sk > 128) and reduce (relb) kernels.
 extern "C" int ct_attn_bwd(const CtAttnCall* call, hipStream_t stream) {
   const CtAttnCall& c = *call;
   if (const int rc = attn_refusal(c, true)) return rc;
@@ -1103,9 +1116,17 @@ extern "C" int ct_attn_bwd(const CtAttnCall* call, hipStream_t stream) {
   const long rows = (long)c.B * c.H * c.Sq;
   const int nkb = (c.Sk + 127) / 128, W = ct_attn_bwd_relbias_window(c.Sq);
   const bool multi = nkb > 1;
-  if (multi && hipMemsetAsync(c.dq_acc, 0, sizeof(float) * rows * 64, stream) != hipSuccess) return -8;
+  if (multi && hipMemsetAsync(c.dq_acc, 0, sizeof(float) * rows * c.D, stream) != hipSuccess) return -8;
   const dim3 grid(nkb, c.B * c.H);
-  if (rel) {
+  if (c.D == 128) {
+    const size_t dyn = rel ? (size_t)W * 2 * sizeof(float) : 0;
+    auto launch = [&](auto MU, auto RE) {
+      with_bools(drop, causal, [&](auto DR, auto CA) {
+        attn_bwd_d128_kernel<DR.value, CA.value, MU.value, RE.value><<<grid, 256, dyn, stream>>>(a);
+      });
+    };
+    with_bools(multi, rel, launch);
+  } else if (rel) {
     const size_t dyn = (size_t)W * 2 * sizeof(float);
     auto launch = [&](auto MU) {
       with_bools(drop, causal, [&](auto DR, auto CA) {
@@ -1126,8 +1147,8 @@ extern "C" int ct_attn_bwd(const CtAttnCall* call, hipStream_t stream) {
   }
   if (launch_rc()) return -8;
   if (multi)
-    attn_dq_convert_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
-        c.dq_acc, a.dq, a.dq_sb, a.dq_ss, a.dq_sh, c.B, c.H, c.Sq);
+    attn_dq_convert_kernel<<<(int)((rows * c.D + 255) / 256), 256, 0, stream>>>(
+        c.dq_acc, a.dq, a.dq_sb, a.dq_ss, a.dq_sh, c.B, c.H, c.Sq, c.D == 128 ? 7 : 6);
   // window of key block 0 starts at offset 1 - 32 nq + rel_base = rel_base + 128 - W
   if (rel)
     attn_drel_reduce_kernel<<<(c.H * c.relb_len + 255) / 256, 256, 0, stream>>>(

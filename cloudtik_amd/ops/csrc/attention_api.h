@@ -23,10 +23,10 @@ struct CtAttnCall {
   const float* relb; long relb_sh; int relb_len, rel_base;
   float* d_rel; long d_sh, d_si;      // backward with relb: its gradient [H, relb_len], any strides
   float* lse;                         // [B * H, Sq] log2-domain; the forward writes, the backward reads
-  // backward workspaces: delta float[B H Sq] (without relb); dq_acc float[B H Sq 64] when Sk > 128;
+  // backward workspaces: delta float[B H Sq] (without relb); dq_acc float[B H Sq D] when Sk > 128;
   // drel_ws float[B ceil(Sk / 128) H ct_attn_bwd_relbias_window(Sq)] (with relb).  None needs clearing.
   float *delta, *dq_acc, *drel_ws;
-  int B, H, Sq, Sk, D;                // D: 64, or 128 (forward only, no dropout)
+  int B, H, Sq, Sk, D;                // D: 64 or 128
   float scale, p_drop; uint64_t seed, offset;
   int causal;
 };
@@ -37,6 +37,8 @@ static_assert(std::is_standard_layout<CtAttnCall>::value && std::is_trivially_co
 // has written nothing and launched nothing.
 extern "C" int ct_attn_fwd(const CtAttnCall* c, hipStream_t stream);
 extern "C" int ct_attn_bwd(const CtAttnCall* c, hipStream_t stream);
-// offsets in one workgroup's window of the bias gradient, and the most the LDS budget takes
+// offsets in one workgroup's window of the bias gradient, and the most the LDS budget takes: at
+// head dim 64, and at head dim D (64 or 128)
 extern "C" int ct_attn_bwd_relbias_window(int Sq);
 extern "C" int ct_attn_bwd_relbias_max_window();
+extern "C" int ct_attn_bwd_relbias_max_window_d(int D);

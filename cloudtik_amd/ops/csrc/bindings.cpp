@@ -391,13 +391,15 @@ std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor dlogits, int64_t 
 // ---------------------------------------------------------------- attention (head_dim 64 / 128)
 // q, k, v, o: 4-D [B, S, H, D] views with unit stride on the last dim (e.g. slices of a
 // packed [B, S, 3, H, D] QKV projection output); key_bias: fp32 [B, Sk] additive.
-// The forward takes D = 64 or D = 128 (the d128 kernel: inference only); the training forward and
-// the backwards D = 64.  Every function fills one CtAttnCall (attention_api.h) through the helpers
+// attn_fwd takes D = 64, or D = 128 without dropout, and attn_bwd D = 64 (the entries of the packed
+// BERT / GPT path and of ops.attention); the training pairs attn_fwd_train / attn_bwd_train and
+// attn_fwd_relbias_train / attn_bwd_relbias take D = 64 or 128.  Every function fills one CtAttnCall (attention_api.h) through the helpers
 // below, each tensor's pointer and strides together, and calls ct_attn_fwd or ct_attn_bwd.
 static CtAttnView attn_view(const at::Tensor& t, const char* name, bool d128) {
   TORCH_CHECK(t.dim() == 4 && (t.size(3) == 64 || (d128 && t.size(3) == 128)) && t.stride(3) == 1, name,
               d128 ? " must be [B,S,H,64] or [B,S,H,128] with unit last stride"
-                   : " must be [B,S,H,64] with unit last stride (the head-dim-128 kernel is forward only)");
+                   : " must be [B,S,H,64] with unit last stride (head dim 128 is forward only through this entry: "
+                     "attn_bwd_train / attn_bwd_relbias take it)");
   CHECK_CUDA(t); CHECK_BF16(t);
   return {t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)};
 }
@@ -409,8 +411,8 @@ static CtAttnCall attn_call(const at::Tensor& q, const at::Tensor& k, const at::
   CtAttnCall c{};
   c.q = attn_view(q, "q", d128); c.k = attn_view(k, "k", d128); c.v = attn_view(v, "v", d128); c.o = attn_view(o, "o", d128);
   if (dO) {
-    c.dO = attn_view(*dO, "dO", false); c.dq = attn_view(*dq, "dq", false);
-    c.dk = attn_view(*dk, "dk", false); c.dv = attn_view(*dv, "dv", false);
+    c.dO = attn_view(*dO, "dO", d128); c.dq = attn_view(*dq, "dq", d128);
+    c.dk = attn_view(*dk, "dk", d128); c.dv = attn_view(*dv, "dv", d128);
   }
   // the head dim the forward dispatches on: q, k, v and o must agree
   const long D = q.size(3);
@@ -465,7 +467,8 @@ at::Tensor attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                     int64_t offset, bool causal) {
   CtAttnCall c = attn_call(q, k, v, o, true);
   key_bias_checked(key_bias, c);
-  TORCH_CHECK(c.D == 64 || p == 0.0, "attn_fwd: the head-dim-128 kernel has no dropout (p must be 0)");
+  TORCH_CHECK(c.D == 64 || p == 0.0, "attn_fwd: head dim 128 has no dropout through this entry (p must be 0; "
+              "attn_fwd_train / attn_fwd_relbias_train take p > 0)");
   // D = 128: no dropout stream, so no seed either
   attn_params(c, scale, p, c.D == 64 ? seed : 0, c.D == 64 ? offset : 0, causal);
   return attn_fwd_run(c, q, "attn_fwd");
@@ -499,12 +502,12 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
   TORCH_CHECK(rc == 0, "attn_bwd failed rc=", rc);
 }
 
-// ---- relative-bias attention for training (T5, head dim 64): forward with dropout + lse, and a
-// backward that also returns the gradient of the bias vector
+// ---- relative-bias attention for training (T5, head dim 64 or 128): forward with dropout + lse,
+// and a backward that also returns the gradient of the bias vector
 at::Tensor attn_fwd_relbias_train(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                   c10::optional<at::Tensor> key_bias, at::Tensor relb, int64_t rel_base,
                                   double scale, double p, int64_t seed, int64_t offset, bool causal) {
-  CtAttnCall c = attn_call(q, k, v, o, false);
+  CtAttnCall c = attn_call(q, k, v, o, true);
   relb_checked(relb, rel_base, c);
   key_bias_checked(key_bias, c);
   attn_params(c, scale, p, seed, offset, causal);
@@ -517,7 +520,7 @@ void attn_bwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at
                       at::Tensor dk, at::Tensor dv, at::Tensor d_rel, c10::optional<at::Tensor> key_bias,
                       at::Tensor relb, int64_t rel_base, at::Tensor lse, double scale, double p, int64_t seed,
                       int64_t offset, bool causal) {
-  CtAttnCall c = attn_call(q, k, v, o, false, &dO, &dq, &dk, &dv);
+  CtAttnCall c = attn_call(q, k, v, o, true, &dO, &dq, &dk, &dv);
   lse_checked(lse, c);
   const long L = relb_checked(relb, rel_base, c);
   key_bias_checked(key_bias, c);
@@ -531,13 +534,38 @@ void attn_bwd_relbias(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at
   const long W = ct_attn_bwd_relbias_window(c.Sq);
   at::Tensor dq_acc, ws;
   // the C entry refuses a longer L and windows past the LDS budget before it touches a workspace
-  const bool sized = L <= kCtAttnRelBiasMax && W <= ct_attn_bwd_relbias_max_window();
-  if (c.Sk > 128 && sized) dq_acc = at::empty({(long)c.B * c.H * c.Sq * 64}, fo);
+  const bool sized = L <= kCtAttnRelBiasMax && W <= ct_attn_bwd_relbias_max_window_d(c.D);
+  if (c.Sk > 128 && sized) dq_acc = at::empty({(long)c.B * c.H * c.Sq * c.D}, fo);
   ws = at::empty({sized ? (long)c.B * nkb * c.H * W : 1L}, fo);
   c.dq_acc = dq_acc.defined() ? dq_acc.data_ptr<float>() : nullptr;
   c.drel_ws = ws.data_ptr<float>();
   int rc = ct_attn_bwd(&c, cur_stream());
   TORCH_CHECK(rc == 0, "attn_bwd_relbias failed rc=", rc);
+}
+
+// ---- attention without a bias vector for training, head dim 64 or 128 (T5 cross-attention at
+// d_kv = 128; at 64 the kernels of attn_fwd / attn_bwd): forward with dropout + lse, and the backward
+at::Tensor attn_fwd_train(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                          c10::optional<at::Tensor> key_bias, double scale, double p, int64_t seed,
+                          int64_t offset, bool causal) {
+  CtAttnCall c = attn_call(q, k, v, o, true);
+  key_bias_checked(key_bias, c);
+  attn_params(c, scale, p, seed, offset, causal);
+  return attn_fwd_run(c, q, "attn_fwd_train");
+}
+
+void attn_bwd_train(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dO, at::Tensor dq,
+                    at::Tensor dk, at::Tensor dv, c10::optional<at::Tensor> key_bias, at::Tensor lse,
+                    double scale, double p, int64_t seed, int64_t offset, bool causal) {
+  CtAttnCall c = attn_call(q, k, v, o, true, &dO, &dq, &dk, &dv);
+  lse_checked(lse, c);
+  key_bias_checked(key_bias, c);
+  attn_params(c, scale, p, seed, offset, causal);
+  at::Tensor dq_acc;
+  if (c.Sk > 128) dq_acc = at::empty({(long)c.B * c.H * c.Sq * c.D}, q.options().dtype(at::kFloat));
+  c.dq_acc = dq_acc.defined() ? dq_acc.data_ptr<float>() : nullptr;
+  int rc = ct_attn_bwd(&c, cur_stream());
+  TORCH_CHECK(rc == 0, "attn_bwd_train failed rc=", rc);
 }
 
 void register_ext(pybind11::module& m);   // bindings_ext.cpp
@@ -599,4 +627,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd_relbias", &attn_bwd_relbias);
   m.def("attn_bwd_relbias_window", [](int64_t Sq) { return (int64_t)ct_attn_bwd_relbias_window((int)Sq); });
   m.def("attn_bwd_relbias_max_window", []() { return (int64_t)ct_attn_bwd_relbias_max_window(); });
+  m.def("attn_bwd_relbias_max_window_d", [](int64_t D) { return (int64_t)ct_attn_bwd_relbias_max_window_d((int)D); });
+  m.def("attn_fwd_train", &attn_fwd_train);
+  m.def("attn_bwd_train", &attn_bwd_train);
 }

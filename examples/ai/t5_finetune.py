@@ -8,7 +8,7 @@
     cloudtik-run --nproc 8 examples/ai/t5_finetune.py --size base --batch 16
 
 The other half of the reference's T5 entry (HF ``run_translation.py --do_train``).  d_kv-64
-topologies (t5-small, t5-base, t5-large) train end to end on the MFMA attention kernels: the
+topologies (t5-small, t5-base, t5-large) and d_kv-128 ones (a t5-3b / t5-11b checkpoint, or ``--d-kv 128``) train end to end on the MFMA attention kernels: the
 relative-position bias is added inside the kernel, whose backward also returns the gradient of the
 bias vector, and both self- and cross-attention take dropout there.  ``CLOUDTIK_AMD_T5_TRAIN_ATTN=0``
 sends those calls to ``F.scaled_dot_product_attention`` instead.
