@@ -1,22 +1,27 @@
-"""T5 encoder-decoder (t5-small / base / large / 3b / 11b topologies; 3b and 11b have d_kv = 128).
+"""T5 encoder-decoder: the v1.0 checkpoints (t5-small / base / large / 3b / 11b; 3b and 11b have
+d_kv = 128) and T5 v1.1 / Flan-T5 (``T5Config.v1_1``: small .. xxl, gated-GELU feed-forward, untied
+output head).
 
 Reference workload: the quickstart T5 inference (applications/ai/quickstart, HF
 ``T5ForConditionalGeneration``).  Random-init weights or a local HF
-checkpoint (``from_hf_config`` / ``load_hf_state_dict``), same architecture:
-pre-norm blocks with RMS LayerNorm (no mean, no bias), un-scaled attention with a learned
-bucketed relative-position bias shared by all layers of a stack, ReLU (v1.0) or gated-GELU
-(v1.1) feed-forward, tied input/output embeddings scaled by d_model^-0.5.
+checkpoint directory (``from_pretrained``; or ``from_hf_config`` + ``load_hf_state_dict``), same
+architecture: pre-norm blocks with RMS LayerNorm (no mean, no bias), un-scaled attention with a
+learned bucketed relative-position bias shared by all layers of a stack, ReLU (v1.0) or gated-GELU
+(v1.1) feed-forward, and an output head that is either the input embedding scaled by d_model^-0.5
+(v1.0, ``tie_word_embeddings``) or a matrix of its own applied unscaled (v1.1, ``lm_head``).
 
 MI355X mapping: RMS norms run in the HIP LayerNorm kernel (``rms=True``); the relative
 position bias is carried as one [H, Sq + Sk - 1] vector per stack (bias depends only on
 key - query) and added inside the MFMA flash-attention kernel (``ops.attention_relbias``),
 so neither inference nor d_kv-64 training materialises an [H, Sq, Sk] bias: the kernels'
 backward returns the gradient of that vector (not bitwise reproducible: fp32 LDS adds) and both
-directions take attention dropout; cross-attention uses the MFMA kernel with the per-key padding
-mask; every attention that needs a gradient at d_kv = 128 uses SDPA with the gathered bias (the
-head-dim-128 kernel is forward only); the training loss is the fused linear + cross-entropy HIP
-kernel over the 32128-token vocabulary; generation keeps a per-layer KV cache and replays
-the decode step as a HIP graph, greedy, with beam search (``ops/beam.py``, ``csrc/beam.hip``) or
+directions take attention dropout, at d_kv 64 and 128 alike; cross-attention uses the MFMA kernel
+with the per-key padding mask; the gated-GELU feed-forward runs ``gelu_tanh(wi_0 x) * wi_1 x`` and its
+dropout as one kernel forward and one backward (``ops.gated_gelu``, ``csrc/gated_act.hip``: only the two
+GEMM outputs are kept for the backward; ``CLOUDTIK_AMD_T5_FUSED_FF=0`` restores the PyTorch
+composition); the training loss is the fused linear + cross-entropy HIP kernel over the
+32128-token vocabulary, on ``lm_head`` when the head is untied; generation keeps a per-layer KV
+cache and replays the decode step as a HIP graph, greedy, with beam search (``ops/beam.py``, ``csrc/beam.hip``) or
 sampling (``ops/sampling.py``, ``csrc/sampling.hip``), each with the history-dependent token bans of
 ``no_repeat_ngram_size``, ``min_length`` and ``bad_words_ids`` (``ops/constrain.py``,
 ``csrc/constrain.hip``).
@@ -57,6 +62,12 @@ class T5Config:
     pad_token_id: int = 0
     decoder_start_token_id: int = 0
     eos_token_id: int = 1
+    tie_word_embeddings: bool = True  # False: an output head of its own, ``lm_head`` (T5 v1.1)
+    scale_decoder_outputs: Optional[bool] = None   # d_model^-0.5 before the head; None: as tie_word_embeddings
+
+    @property
+    def scales_outputs(self) -> bool:
+        return self.tie_word_embeddings if self.scale_decoder_outputs is None else bool(self.scale_decoder_outputs)
 
     @classmethod
     def small(cls, **kw):
@@ -81,12 +92,27 @@ class T5Config:
         return cls(d_model=1024, d_kv=128, d_ff=65536, num_layers=24, num_decoder_layers=24, num_heads=128, **kw)
 
     @classmethod
+    def v1_1(cls, size: str, **kw):
+        """T5 v1.1 / Flan-T5 ``small`` .. ``xxl``: gated-GELU feed-forward, untied unscaled head."""
+        if size not in _V1_1_SIZES:
+            raise ValueError(f"unknown T5 v1.1 size {size!r} (known: {', '.join(_V1_1_SIZES)})")
+        d_model, d_ff, layers, heads = _V1_1_SIZES[size]
+        base = dict(d_model=d_model, d_kv=64, d_ff=d_ff, num_layers=layers, num_decoder_layers=layers, num_heads=heads,
+                    gated_gelu=True, tie_word_embeddings=False)
+        base.update(kw)
+        return cls(**base)
+
+    @classmethod
     def tiny(cls, **kw):
         base = dict(vocab_size=64, d_model=32, d_kv=8, d_ff=64, num_layers=2, num_decoder_layers=2, num_heads=4,
                     relative_attention_num_buckets=8, relative_attention_max_distance=16, dropout_rate=0.0)
         base.update(kw)
         return cls(**base)
 
+
+# T5 v1.1 / Flan-T5: (d_model, d_ff, layers per stack, heads); d_kv is 64 throughout
+_V1_1_SIZES = {"small": (512, 1024, 8, 6), "base": (768, 2048, 12, 12), "large": (1024, 2816, 24, 16),
+               "xl": (2048, 5120, 24, 32), "xxl": (4096, 10240, 24, 64)}
 
 _TASK_PASS_THROUGH = ("min_length", "no_repeat_ngram_size", "num_beams", "length_penalty", "early_stopping")
 
@@ -121,6 +147,37 @@ def generate_kwargs_for_task(config, task: str):
     return kwargs, prefix
 
 
+def _read_checkpoint(path: str):
+    """The state dict of a local HF checkpoint directory, single file or sharded."""
+    import json
+
+    def load(name):
+        f = os.path.join(path, name)
+        if name.endswith(".safetensors"):
+            from safetensors.torch import load_file
+            return load_file(f)
+        return torch.load(f, map_location="cpu", weights_only=True)
+
+    for single, index in (("model.safetensors", "model.safetensors.index.json"),
+                          ("pytorch_model.bin", "pytorch_model.bin.index.json")):
+        if os.path.exists(os.path.join(path, single)):
+            return load(single)
+        if os.path.exists(os.path.join(path, index)):
+            with open(os.path.join(path, index)) as f:
+                weight_map = json.load(f)["weight_map"]
+            sd = {}
+            for shard in sorted(set(weight_map.values())):
+                if os.path.basename(shard) != shard:
+                    raise ValueError(f"{index} names a shard outside the checkpoint directory: {shard!r}")
+                part = load(shard)
+                sd.update({k: v for k, v in part.items() if weight_map.get(k) == shard})
+            missing = sorted(set(weight_map) - set(sd))
+            if missing:
+                raise KeyError(f"{index} lists tensors its shards do not hold: {missing}")
+            return sd
+    raise FileNotFoundError(f"no model.safetensors, pytorch_model.bin or sharded index in {path!r}")
+
+
 def relative_position_bucket(rel: torch.Tensor, bidirectional: bool, num_buckets: int, max_distance: int):
     """T5 bucketing of (key - query) offsets: exact buckets for small offsets, log-spaced
     buckets up to ``max_distance``, one shared bucket beyond."""
@@ -144,6 +201,13 @@ def train_attention_kernels() -> bool:
     ``CLOUDTIK_AMD_T5_TRAIN_ATTN=0`` keeps those calls on ``F.scaled_dot_product_attention`` with
     a materialised bias, the earlier routing (the A/B switch of bench/t5_train_probe.py)."""
     return os.environ.get("CLOUDTIK_AMD_T5_TRAIN_ATTN", "1") != "0"
+
+
+def fused_ff_kernels() -> bool:
+    """Whether the gated-GELU feed-forward takes ``ops.gated_gelu`` on the GPU in bf16 (default);
+    ``CLOUDTIK_AMD_T5_FUSED_FF=0`` keeps the PyTorch composition, the earlier routing (the A/B switch
+    of bench/t5_ff_probe.py).  Read per call."""
+    return os.environ.get("CLOUDTIK_AMD_T5_FUSED_FF", "1") != "0"
 
 
 class T5Norm(nn.Module):
@@ -258,8 +322,29 @@ class T5FF(nn.Module):
             self.wi_1 = nn.Linear(cfg.d_model, cfg.d_ff, **kw)
         self.wo = nn.Linear(cfg.d_ff, cfg.d_model, **kw)
         self.p = cfg.dropout_rate
+        self.d_ff = cfg.d_ff
+
+    def fused(self, x) -> bool:
+        """Whether ``x`` takes the gated-GELU kernel: a gated feed-forward on the GPU in bf16.  One row
+        through the float linears in inference (greedy decoding of one source) stays on the composition:
+        the kernel measured 0.5 % slower per token there and faster everywhere else
+        (profiles/t5_v11/SUMMARY.md).  The int8 linears take the kernel at every row count, in the module
+        path and in the fused decode step alike."""
+        if not (self.gated and x.is_cuda and x.dtype == torch.bfloat16 and self.d_ff % 8 == 0 and fused_ff_kernels()):
+            return False
+        one_row = x.numel() == x.shape[-1]
+        return not (one_row and not self.training and isinstance(self.wi, nn.Linear))
+
+    def gate(self, g, u):
+        """gelu_tanh(g) * u without dropout: the activation of the inference steps (the int8 decode
+        step calls it on the halves of its stacked GEMM output, so both paths give the same bits)."""
+        if self.fused(g):
+            return ops.gated_gelu(g, u, 0.0, False)
+        return F.gelu(g, approximate="tanh") * u
 
     def forward(self, x):
+        if self.fused(x):
+            return self.wo(ops.gated_gelu(self.wi(x), self.wi_1(x), self.p, self.training))
         h = F.gelu(self.wi(x), approximate="tanh") * self.wi_1(x) if self.gated else F.relu(self.wi(x))
         if self.training and self.p:
             h = F.dropout(h, self.p)
@@ -334,7 +419,14 @@ class T5ForConditionalGeneration(nn.Module):
         nn.init.normal_(self.shared.weight, std=1.0)
         self.encoder = T5Stack(cfg, False, self.shared, device, dtype)
         self.decoder = T5Stack(cfg, True, self.shared, device, dtype)
+        if not cfg.tie_word_embeddings:
+            self.lm_head = nn.Linear(cfg.d_model, cfg.vocab_size, bias=False, device=device, dtype=dtype)
+            nn.init.normal_(self.lm_head.weight, std=1.0)      # the library's init of an untied head
         self.dtype = dtype
+
+    def head_weight(self):
+        """The output head [vocab, d_model]: ``lm_head`` of an untied model, else the embedding."""
+        return self.shared.weight if self.cfg.tie_word_embeddings else self.lm_head.weight
 
     def _shift_right(self, labels):
         start = torch.full_like(labels[:, :1], self.cfg.decoder_start_token_id)
@@ -342,15 +434,20 @@ class T5ForConditionalGeneration(nn.Module):
         return ids.masked_fill(ids == -100, self.cfg.pad_token_id)
 
     def forward(self, input_ids, labels, attention_mask=None, decoder_input_ids=None):
-        """Training: mean token cross-entropy (tied, d_model^-0.5-scaled output head)."""
+        """Training: mean token cross-entropy (the tied head scaled by d_model^-0.5, or the untied
+        ``lm_head`` unscaled: ``cfg.scales_outputs``)."""
         enc, _ = self.encoder(input_ids, attention_mask)
         dec_ids = decoder_input_ids if decoder_input_ids is not None else self._shift_right(labels)
         dec, _ = self.decoder(dec_ids, enc=enc, enc_mask=attention_mask)
-        x = (dec * (self.cfg.d_model ** -0.5)).reshape(-1, self.cfg.d_model)
-        return ops.cross_entropy_fused(x, self.shared.weight, None, labels.reshape(-1), ignore_index=-100)
+        if self.cfg.scales_outputs:
+            dec = dec * (self.cfg.d_model ** -0.5)
+        x = dec.reshape(-1, self.cfg.d_model)
+        return ops.cross_entropy_fused(x, self.head_weight(), None, labels.reshape(-1), ignore_index=-100)
 
     def logits(self, dec):
-        return F.linear(dec * (self.cfg.d_model ** -0.5), self.shared.weight)
+        if self.cfg.scales_outputs:
+            dec = dec * (self.cfg.d_model ** -0.5)
+        return F.linear(dec, self.head_weight())
 
     def quantize_dynamic(self):
         """The int8 inference model of this one (``models.t5_quant``; the reference's
@@ -842,9 +939,36 @@ class T5ForConditionalGeneration(nn.Module):
 
     # --------------------------------------------------------------------- pretrained weights
     @classmethod
-    def from_hf_config(cls, config, device=None, dtype=torch.bfloat16):
+    def from_pretrained(cls, path, device=None, dtype=torch.bfloat16):
+        """The model of a local HF checkpoint directory (nothing is ever downloaded): ``config.json`` and
+        the weights in ``model.safetensors``, ``pytorch_model.bin``, or the shards that
+        ``model.safetensors.index.json`` / ``pytorch_model.bin.index.json`` list.  The head is untied when
+        the config says ``tie_word_embeddings: false`` or the weights hold an ``lm_head.weight`` that differs
+        from ``shared.weight`` (newer versions of the library save an untied model as ``tie_word_embeddings:
+        true, scale_decoder_outputs: false`` plus that tensor); ``scale_decoder_outputs`` is the config's
+        when it has one, else that of a tied head exactly."""
+        import json
+        path = os.fspath(path)
+        if not os.path.isdir(path):
+            raise FileNotFoundError(f"from_pretrained takes a local checkpoint directory, got {path!r}")
+        with open(os.path.join(path, "config.json")) as f:
+            config = json.load(f)
+        sd = _read_checkpoint(path)
+        head, shared = sd.get("lm_head.weight"), sd.get("shared.weight")
+        differs = head is not None and shared is not None and (head.shape != shared.shape or not torch.equal(head, shared))
+        tie = config.get("tie_word_embeddings")
+        untied = differs or (tie is not None and not tie)
+        model = cls.from_hf_config({**config, "tie_word_embeddings": not untied}, device=device, dtype=dtype,
+                                   untied_head=untied)
+        return model.load_hf_state_dict(sd)
+
+    @classmethod
+    def from_hf_config(cls, config, device=None, dtype=torch.bfloat16, untied_head: bool = False):
         """A model with the topology of a HF T5 config: a ``T5Config`` of the library, a dict, or
-        the path of a local ``config.json``."""
+        the path of a local ``config.json``.  ``untied_head``: an output head of its own (``lm_head``,
+        T5 v1.1 / Flan-T5), whatever the config's ``tie_word_embeddings``; without it such a config is
+        refused, since the weights decide too (``from_pretrained`` looks at both).  A
+        ``scale_decoder_outputs`` key is honoured; absent, a tied head scales and an untied one does not."""
         if isinstance(config, (str, os.PathLike)):
             import json
             with open(config) as f:
@@ -859,7 +983,9 @@ class T5ForConditionalGeneration(nn.Module):
         if act not in ("relu", "gated-gelu"):
             raise ValueError(f"unsupported feed_forward_proj {act!r} (relu and gated-gelu are)")
         if not get("tie_word_embeddings", True):
-            raise ValueError("checkpoints with an untied output head (tie_word_embeddings=False) are not supported")
+            if not untied_head:
+                raise ValueError("the config has an untied output head (tie_word_embeddings=False): load the checkpoint "
+                                 "directory with from_pretrained, or pass untied_head=True")
         eos = get("eos_token_id", 1)
         if isinstance(eos, (list, tuple)):
             if len(eos) != 1:
@@ -873,12 +999,15 @@ class T5ForConditionalGeneration(nn.Module):
             relative_attention_max_distance=get("relative_attention_max_distance", 128),
             dropout_rate=get("dropout_rate", 0.1), layer_norm_epsilon=get("layer_norm_epsilon", 1e-6),
             gated_gelu=act == "gated-gelu", pad_token_id=get("pad_token_id", 0),
-            decoder_start_token_id=get("decoder_start_token_id", 0), eos_token_id=eos)
+            decoder_start_token_id=get("decoder_start_token_id", 0), eos_token_id=eos,
+            tie_word_embeddings=not untied_head, scale_decoder_outputs=config.get("scale_decoder_outputs"))
         return cls(cfg, device=device, dtype=dtype)
 
     def _hf_name_map(self):
         """{our parameter name: HF state-dict key}."""
         names = {"shared.weight": "shared.weight"}
+        if not self.cfg.tie_word_embeddings:
+            names["lm_head.weight"] = "lm_head.weight"
         for stack, blocks in (("encoder", self.encoder.blocks), ("decoder", self.decoder.blocks)):
             names[f"{stack}.final.weight"] = f"{stack}.final_layer_norm.weight"
             ff = 2 if stack == "decoder" else 1
@@ -907,7 +1036,8 @@ class T5ForConditionalGeneration(nn.Module):
         """Copy the weights of a HF ``T5ForConditionalGeneration`` state dict (a dict, or the path
         of a local ``.bin`` / ``.pt`` / ``.safetensors`` file) into this model, cast to its dtype.
         Every parameter must be present with its shape, and no key may be left over: the tied
-        copies of the embedding are accepted when they equal it, an untied ``lm_head`` is not."""
+        copies of the embedding are accepted when they equal it; a model with an untied head requires
+        ``lm_head.weight`` and copies it, a tied one refuses an ``lm_head.weight`` that differs."""
         if isinstance(state_dict, (str, os.PathLike)):
             path = os.fspath(state_dict)
             if path.endswith(".safetensors"):
@@ -917,7 +1047,9 @@ class T5ForConditionalGeneration(nn.Module):
                 state_dict = torch.load(path, map_location="cpu", weights_only=True)
         sd = dict(state_dict)
         shared = sd.get("shared.weight")
-        for tied in ("encoder.embed_tokens.weight", "decoder.embed_tokens.weight", "lm_head.weight"):
+        tied_keys = ("encoder.embed_tokens.weight", "decoder.embed_tokens.weight") + \
+            (("lm_head.weight",) if self.cfg.tie_word_embeddings else ())
+        for tied in tied_keys:
             w = sd.pop(tied, None)
             if w is not None and (shared is None or w.shape != shared.shape or not torch.equal(w, shared.to(w.device))):
                 raise ValueError(f"{tied} differs from shared.weight: untied embeddings / output heads are not supported")

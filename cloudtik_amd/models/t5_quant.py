@@ -8,7 +8,8 @@ accumulation.  That is this project's format, not torch's per-tensor affine one,
 the reference's int8 model are not reproduced bit for bit.
 
 What is quantized: every linear of both stacks and the output head (an int8 copy of the tied
-embedding with the d_model^-0.5 folded into its channel scales).  The embedding lookup table, the
+embedding with the d_model^-0.5 folded into its channel scales; of ``lm_head`` with factor 1 for the
+untied unscaled head of T5 v1.1).  The embedding lookup table, the
 norms' weights, the relative-bias table and attention stay in the model dtype.  ``q`` / ``k`` /
 ``v`` of self-attention are one stacked [3 inner, d_model] weight and ``wi_0`` / ``wi_1`` of the gated
 feed-forward one [2 d_ff, d_model] weight; the per-matrix modules the float code calls (``sa.q``,
@@ -32,7 +33,6 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from cloudtik_amd import ops
 from cloudtik_amd.models.t5 import T5Config, T5ForConditionalGeneration, T5Norm, relative_position_bucket
@@ -123,6 +123,8 @@ class QuantT5ForConditionalGeneration(T5ForConditionalGeneration):
                     ff.wi = QuantLinear(cfg.d_model, cfg.d_ff, device)
                 ff.wo = QuantLinear(cfg.d_ff, cfg.d_model, device)
         self.head = QuantLinear(cfg.d_model, cfg.vocab_size, device)
+        if not cfg.tie_word_embeddings:
+            del self.lm_head                   # the untied float head lives on as `head` alone
         for m in self.modules():
             for name, p in list(m._parameters.items()):
                 if p is not None and p.is_meta:
@@ -139,7 +141,7 @@ class QuantT5ForConditionalGeneration(T5ForConditionalGeneration):
         w = model.shared.weight
         q = cls(model.cfg, device=w.device, dtype=model.dtype)
         q.shared.weight.copy_(w)
-        q.head.load_weight(w, model.cfg.d_model ** -0.5)
+        q.head.load_weight(model.head_weight(), model.cfg.d_model ** -0.5 if model.cfg.scales_outputs else None)
         for qs, fs in ((q.encoder, model.encoder), (q.decoder, model.decoder)):
             qs.final.weight.copy_(fs.final.weight)
             for qb, fb in zip(qs.blocks, fs.blocks):
@@ -178,7 +180,7 @@ class QuantT5ForConditionalGeneration(T5ForConditionalGeneration):
     # ------------------------------------------------------------------------------ the head
     def logits(self, dec):
         """[..., vocab] from the final norm's output, a tensor or the fused norm's int8 rows; the
-        d_model^-0.5 of the tied head lives in the head's channel scales."""
+        d_model^-0.5 of a scaled head lives in the head's channel scales."""
         if isinstance(dec, RowQuantized):
             return self.head((dec.q, dec.scale), dtype=self.dtype)
         return self.head(dec)
@@ -218,7 +220,7 @@ class QuantT5ForConditionalGeneration(T5ForConditionalGeneration):
             _, h = quant.rms_norm_quant(x, blk.ln_ff.weight, blk.ln_ff.eps, emit_y=False)
             if ff.gated:
                 g, u = ff.wi_stack(h, dtype=dt).split(cfg.d_ff, -1)
-                h = F.gelu(g, approximate="tanh") * u
+                h = ff.gate(g, u)
             else:
                 h = ff.wi(h, act=quant.ACT_RELU, dtype=dt)
             x = add_into(ff.wo, h, x)

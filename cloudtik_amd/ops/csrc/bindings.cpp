@@ -580,6 +580,7 @@ void register_sampling(pybind11::module& m); // bindings_sampling.cpp
 void register_constrain(pybind11::module& m); // bindings_constrain.cpp
 void register_quant_skinny(pybind11::module& m); // bindings_quant_skinny.cpp
 void register_bn(pybind11::module& m);     // bindings_bn.cpp
+void register_gated_act(pybind11::module& m); // bindings_gated_act.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "cloudtik_amd CDNA4 (gfx950) op library";
@@ -595,6 +596,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_constrain(m);
   register_quant_skinny(m);
   register_bn(m);
+  register_gated_act(m);
   m.def("layernorm_fwd", &layernorm_fwd, pybind11::arg("x"), pybind11::arg("bias"), pybind11::arg("res"),
         pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("eps"), pybind11::arg("rms"),
         pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("offset"), pybind11::arg("keep_sum") = true);

@@ -117,6 +117,67 @@ def dropout(x, p=0.1, training=True):
     return torch.nn.functional.dropout(x, p, True)
 
 
+# ----------------------------------------------------------------------------- gated GELU
+def _rows(t, F):
+    """``t`` [..., F] as [M, F] without a copy where its leading dimensions collapse to one row
+    stride the kernel takes (a multiple of 8 elements, last dimension contiguous)."""
+    if t.stride(-1) == 1 or F == 1:
+        try:
+            r = t.view(-1, F)
+            if r.shape[0] <= 1 or r.stride(0) % 8 == 0:
+                return r
+        except RuntimeError:
+            pass
+    return t.contiguous().view(-1, F)
+
+
+class _GatedGeluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, u, p, seed, offset):
+        F = g.shape[-1]
+        ctx.save_for_backward(g, u)
+        ctx.cfg = (p, seed, offset)
+        return _C().gated_gelu_fwd(_rows(g, F), _rows(u, F), p, seed, offset).view(g.shape)
+
+    @staticmethod
+    def backward(ctx, dh):
+        g, u = ctx.saved_tensors
+        p, seed, offset = ctx.cfg
+        F = g.shape[-1]
+        dh = dh.contiguous()
+        if dh.data_ptr() % 16:
+            dh = dh.clone()
+        dg, du = _C().gated_gelu_bwd(dh.view(-1, F), _rows(g, F), _rows(u, F), p, seed, offset)
+        return dg.view(g.shape), du.view(g.shape), None, None, None
+
+
+def gated_gelu(g, u, p=0.0, training=True):
+    """h = dropout_p(gelu_tanh(g) * u), the gated-GELU feed-forward activation of T5 v1.1.
+
+    GPU: bf16 ``[..., F]`` with ``F % 8 == 0`` and 16-byte-aligned bases in one kernel forward and one
+    backward (the sigmoid and the keep bits are recomputed: only ``g`` and ``u`` are saved); the
+    halves of a stacked ``[M, 2F]`` tensor go in without a copy.  Anything else on the GPU raises.
+    The dropout mask is the one ``ops.dropout`` draws for a tensor of the output's shape."""
+    if g.shape != u.shape or g.dtype != u.dtype or g.device != u.device:
+        raise ValueError(f"gated_gelu: g and u must agree in shape, dtype and device, got {tuple(g.shape)} {g.dtype} "
+                         f"{g.device} and {tuple(u.shape)} {u.dtype} {u.device}")
+    p = float(p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"gated_gelu: p must be in [0, 1), got {p}")
+    seed, offset = _pkg()._rng.next(g.numel()) if p > 0 else (0, 0)
+    if _native(g):
+        if g.dtype != torch.bfloat16:
+            raise ValueError(f"gated_gelu: the GPU kernel takes bf16, got {g.dtype}")
+        if g.dim() < 1 or g.shape[-1] % 8 or g.shape[-1] == 0:
+            raise ValueError(f"gated_gelu: the GPU kernel needs a last dimension that is a multiple of 8, got {tuple(g.shape)}")
+        if g.data_ptr() % 16 or u.data_ptr() % 16:
+            raise ValueError("gated_gelu: the GPU kernel needs 16-byte-aligned base addresses")
+        return _GatedGeluFn.apply(g, u, p, seed, offset)
+    if p > 0 and g.numel() % 8:
+        raise ValueError(f"gated_gelu: the hash dropout mask needs numel % 8 == 0, got {g.numel()}")
+    return ref.gated_gelu(g, u, p, seed, offset)
+
+
 # ----------------------------------------------------------------------------- embeddings
 class _Embed3Fn(torch.autograd.Function):
     @staticmethod

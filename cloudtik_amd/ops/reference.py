@@ -103,6 +103,12 @@ def bias_act(z, bias=None, act=ACT_GELU):
     return t.to(z.dtype)
 
 
+def gated_gelu(g, u, p=0.0, seed=0, offset=0):
+    """h = dropout_p(gelu_tanh(g) * u) in the input dtype, the hash mask of (seed, offset) over
+    the contiguous output (T5 v1.1 feed-forward)."""
+    return dropout(F.gelu(g, approximate="tanh") * u, p, seed, offset)
+
+
 def embedding3(ids, tt, W, P=None, T=None):
     out = W.float()[ids]
     if P is not None:

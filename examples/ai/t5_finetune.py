@@ -5,13 +5,16 @@
     python examples/ai/t5_finetune.py --size tiny --max-steps 40 --lr 3e-3 --eval-generate 2
     python examples/ai/t5_finetune.py --checkpoint /models/t5-small --data pairs.jsonl --epochs 3
     python examples/ai/t5_finetune.py --checkpoint /models/t5-small --text-file en_de.tsv --eval-generate 4
+    python examples/ai/t5_finetune.py --checkpoint /models/flan-t5-base --text-file qa.tsv
     cloudtik-run --nproc 8 examples/ai/t5_finetune.py --size base --batch 16
 
 The other half of the reference's T5 entry (HF ``run_translation.py --do_train``).  d_kv-64
 topologies (t5-small, t5-base, t5-large) and d_kv-128 ones (a t5-3b / t5-11b checkpoint, or ``--d-kv 128``) train end to end on the MFMA attention kernels: the
 relative-position bias is added inside the kernel, whose backward also returns the gradient of the
 bias vector, and both self- and cross-attention take dropout there.  ``CLOUDTIK_AMD_T5_TRAIN_ATTN=0``
-sends those calls to ``F.scaled_dot_product_attention`` instead.
+sends those calls to ``F.scaled_dot_product_attention`` instead.  T5 v1.1 / Flan-T5 checkpoints (and
+``--size v1.1-small`` .. ``v1.1-xxl``) train their untied head and run the gated-GELU feed-forward with its
+dropout as one kernel forward and one backward (``CLOUDTIK_AMD_T5_FUSED_FF=0``: the PyTorch composition).
 
 Training pairs, in this order of preference:
 
@@ -21,8 +24,8 @@ Training pairs, in this order of preference:
 * otherwise a seeded synthetic copy task: random sources, the target is the source followed by EOS.
 
 Batches are padded to their longest source and target, with ``attention_mask`` and ``-100`` labels.
-``--checkpoint`` is a directory holding ``config.json`` and ``model.safetensors`` or
-``pytorch_model.bin``; ``--size`` selects a random-init topology (``--d-kv`` / ``--dropout`` override
+``--checkpoint`` is a directory holding ``config.json`` and ``model.safetensors``, ``pytorch_model.bin`` or
+a sharded checkpoint with its index (``T5ForConditionalGeneration.from_pretrained``); ``--size`` selects a random-init topology (``--d-kv`` / ``--dropout`` override
 it).  Trains through ``cloudtik_amd.train.trainer.Trainer`` with the fused AdamW, prints the loss
 every ``--log-every`` steps and one JSON result line, and with ``--eval-generate N`` prints greedy
 outputs for N sources at the end.
@@ -38,6 +41,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 
+_V1_1 = ["v1.1-small", "v1.1-base", "v1.1-large", "v1.1-xl", "v1.1-xxl"]
+
+
 def load_model(checkpoint, size, device, dtype, d_kv=None, dropout=None):
     from cloudtik_amd.models.t5 import T5Config, T5ForConditionalGeneration
     if checkpoint is None:
@@ -46,15 +52,12 @@ def load_model(checkpoint, size, device, dtype, d_kv=None, dropout=None):
             kw["d_kv"] = d_kv
         if dropout is not None:
             kw["dropout_rate"] = dropout
-        return T5ForConditionalGeneration(getattr(T5Config, size)(**kw), device=device, dtype=dtype)
-    model = T5ForConditionalGeneration.from_hf_config(os.path.join(checkpoint, "config.json"), device=device, dtype=dtype)
+        cfg = T5Config.v1_1(size[len("v1.1-"):], **kw) if size.startswith("v1.1-") else getattr(T5Config, size)(**kw)
+        return T5ForConditionalGeneration(cfg, device=device, dtype=dtype)
+    model = T5ForConditionalGeneration.from_pretrained(checkpoint, device=device, dtype=dtype)
     if dropout is not None:
         model.cfg.dropout_rate = dropout
-    for name in ("model.safetensors", "pytorch_model.bin"):
-        path = os.path.join(checkpoint, name)
-        if os.path.exists(path):
-            return model.load_hf_state_dict(path)
-    raise FileNotFoundError(f"no model.safetensors or pytorch_model.bin in {checkpoint}")
+    return model
 
 
 def load_tokenizer(checkpoint):
@@ -130,7 +133,7 @@ class PairLoader:
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint", default=None, help="local directory with config.json and the weights")
-    ap.add_argument("--size", default="small", choices=["tiny", "small", "base", "large"], help="random-init topology")
+    ap.add_argument("--size", default="small", choices=["tiny", "small", "base", "large"] + _V1_1, help="random-init topology")
     ap.add_argument("--d-kv", type=int, default=None, help="override the topology's head dim (random init)")
     ap.add_argument("--dropout", type=float, default=None, help="override the dropout rate")
     ap.add_argument("--data", default=None, help='JSON lines of {"input_ids": [...], "labels": [...]}')

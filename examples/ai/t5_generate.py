@@ -8,6 +8,8 @@
     python examples/ai/t5_generate.py --no-repeat-ngram-size 3 --min-length 8 --bad-words 5 --bad-words 17,42
     python examples/ai/t5_generate.py --checkpoint /models/t5-small --task summarization --text "..."
     python examples/ai/t5_generate.py --precision int8                  # every linear and the head in int8
+    python examples/ai/t5_generate.py --checkpoint /models/flan-t5-base --text "Answer: is water wet?"
+    python examples/ai/t5_generate.py --size v1.1-base                  # T5 v1.1 / Flan-T5 topology, random weights
 
 ``--task`` takes the generation settings the checkpoint's ``config.json`` ships for that task
 (``task_specific_params``: beams, length penalty, minimum length, n-gram ban, ...) and puts the
@@ -17,8 +19,9 @@ task's prefix in front of every ``--text``; flags given on the command line are 
 int8 weights with one scale per output channel, activations quantized per token on every call)
 and generates with that; every mode and flag works as on the bf16 model.
 
-``--checkpoint`` is a directory holding ``config.json`` and ``model.safetensors`` or
-``pytorch_model.bin`` (nothing is downloaded).  With a ``spiece.model`` in it and the
+``--checkpoint`` is a directory holding ``config.json`` and ``model.safetensors``, ``pytorch_model.bin``
+or a sharded checkpoint with its index (``T5ForConditionalGeneration.from_pretrained``; nothing is
+downloaded): T5 v1.0, or T5 v1.1 / Flan-T5 with the gated-GELU feed-forward and an untied head.  With a ``spiece.model`` in it and the
 ``transformers`` tokenizer installed, ``--text`` is tokenized and the output decoded; otherwise
 random token ids go in and token ids are printed.  Runs on the GPU when there is one.
 """
@@ -32,19 +35,23 @@ import torch  # noqa: E402
 
 
 _SIZES = {"3b": "xl", "11b": "xxl"}         # --size name -> T5Config constructor
+_V1_1 = ["v1.1-small", "v1.1-base", "v1.1-large", "v1.1-xl", "v1.1-xxl"]
+
+
+def size_config(size, **kw):
+    """The T5Config of a ``--size`` name."""
+    from cloudtik_amd.models.t5 import T5Config
+    if size.startswith("v1.1-"):
+        return T5Config.v1_1(size[len("v1.1-"):], **kw)
+    return getattr(T5Config, _SIZES.get(size, size))(**kw)
 
 
 def load_model(checkpoint, size, device, dtype):
-    from cloudtik_amd.models.t5 import T5Config, T5ForConditionalGeneration
+    from cloudtik_amd.models.t5 import T5ForConditionalGeneration
     if checkpoint is None:
         torch.manual_seed(0)
-        return T5ForConditionalGeneration(getattr(T5Config, _SIZES.get(size, size))(dropout_rate=0.0), device=device, dtype=dtype).eval()
-    model = T5ForConditionalGeneration.from_hf_config(os.path.join(checkpoint, "config.json"), device=device, dtype=dtype)
-    for name in ("model.safetensors", "pytorch_model.bin"):
-        path = os.path.join(checkpoint, name)
-        if os.path.exists(path):
-            return model.load_hf_state_dict(path).eval()
-    raise FileNotFoundError(f"no model.safetensors or pytorch_model.bin in {checkpoint}")
+        return T5ForConditionalGeneration(size_config(size, dropout_rate=0.0), device=device, dtype=dtype).eval()
+    return T5ForConditionalGeneration.from_pretrained(checkpoint, device=device, dtype=dtype).eval()
 
 
 def load_tokenizer(checkpoint):
@@ -61,7 +68,8 @@ def load_tokenizer(checkpoint):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint", default=None, help="local directory with config.json and the weights")
-    ap.add_argument("--size", default="small", choices=["tiny", "small", "base", "large", "3b", "11b"], help="random-init topology")
+    ap.add_argument("--size", default="small", choices=["tiny", "small", "base", "large", "3b", "11b"] + _V1_1,
+                    help="random-init topology")
     ap.add_argument("--text", action="append", help="source sentence (repeatable; needs the tokenizer)")
     ap.add_argument("--batch", type=int, default=2, help="random sources when there is no text")
     ap.add_argument("--source-len", type=int, default=24)
